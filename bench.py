@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: RePo world-model + imagination updates per second.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5|c4x128|tia|mt]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5|c4x128|tia|mt] [--dump-outputs DIR] [--full]
 
 Workload (default `--config c2` = BASELINE.json configs[1]): algo=repo, B=50
 sequences per GPU, L=50, H=15, A=6, 64x64x3 uint8 frames, parameters at torch default init under
@@ -10,12 +10,18 @@ torch.manual_seed(0), fp32 arithmetic.  One step = ONE iteration of the referenc
 four optimiser steps and the noise generation inside the timed region.  The synthetic replay ring
 (RandomState(1234+rank)) is mirrored in HBM before the timed region starts (repo_amd/common/buffers.py:
 the sampler draws indices on the host exactly like the reference, the 30.7 MB batch is gathered on the
-device), so `value` is the rate with inputs resident in HBM; the same K steps on ONE resident batch are
-timed afterwards and reported as `resident_batch_ms` (what round 1's line measured).
+device), so `value` is the rate with inputs resident in HBM.
+
+A plain run sets up, runs W warm-up and K timed steps and prints the line; nothing else runs on the GPU or the host.
+--dump-outputs DIR writes what the last timed step handed its caller (see dump_outputs()); every input is seeded, so
+two runs with the same arguments start from identical inputs.  --full adds every other figure of the line, each
+measured after the timed steps: the same K steps on ONE resident batch (`resident_batch_ms`, what round 1's line
+measured), the pinned host path (`pinned_path_ms`), `roofline`, and with N > 1 `strong` and `allreduce_ms`, and the
+CPU oracle (`cpu_baseline`, unless --no-cpu-baseline).
 
 N > 1: data parallel over batch rows, RCCL all-reduce of the flat gradient buffers (model gradient in two
 buckets overlapped with the encoder backward, actor + critic in one).  `value` is WEAK scaling (B=50 per GPU,
-global batch 50*N); the same line carries a `strong` object: ONE global batch of 50 sequences dealt 7,7,6,...
+global batch 50*N); with --full the same line carries a `strong` object: ONE global batch of 50 sequences dealt 7,7,6,...
 over the ranks (BASELINE's "updates/sec (B=50 ...) at 1/2/4/8"), each rank sampling its shard from its ring,
 timed the same way (barrier + synchronize on both sides, max over ranks), plus the per-rank time spent inside
 the all-reduces (`allreduce_ms`, HIP events around the collectives of the weak run).  `python bench.py --gpus N`
@@ -499,6 +505,33 @@ def cpu_baseline(threads=None, warm=2, timed=3, timeout_s=240.0, B=50, A=6, algo
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(agent, scalars, out_dir):
+    """--dump-outputs: what the last timed update handed its caller, one .npy per array -- every logged scalar
+    (`scalar.<name>`, float64) and every trained tensor of the checkpoint dict (`param.<module>.<tensor>`, float32;
+    get_param_dict() without the optimiser moments).  Above DUMP_LIMIT_BYTES in all, every array of more than 4096
+    elements is cut to the same fraction of its elements by a fixed RandomState(0) sample (sorted flat indices), so two
+    builds stay comparable."""
+    arrays = {f"scalar.{k.replace('/', '.')}": np.asarray(float(v), dtype=np.float64) for k, v in scalars.items()}
+    for name, val in agent.get_param_dict().items():
+        if name.endswith("_optimizer") or not (isinstance(val, dict) or torch.is_tensor(val)):
+            continue
+        for k, t in (val.items() if isinstance(val, dict) else [(None, val)]):
+            arrays[f"param.{name}" + (f".{k}" if k else "")] = t.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        big = {k: a for k, a in arrays.items() if a.size > 4096}
+        big_bytes = sum(a.nbytes for a in big.values())
+        frac = (DUMP_LIMIT_BYTES - (total - big_bytes) - 4096 * len(arrays)) / big_bytes   # 4096: room for .npy headers
+        for k, a in big.items():
+            arrays[k] = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, int(a.size * frac), replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------- self-launch (N > 1)
 def _free_port():
     s = socket.socket()
@@ -519,13 +552,16 @@ def launch_ranks(n):
     return subprocess.run(cmd, env=env).returncode
 
 
-def rendezvous_only(world, rank):
-    """--rendezvous-only: the launcher / process-group plumbing without the workload (gloo when there is no
-    GPU), so the self-launch path is testable on a CPU-only box."""
+def rendezvous_only(world, rank, local_rank):
+    """--rendezvous-only: the launcher / process-group plumbing without the workload (gloo unless every rank has a
+    GPU of its own: RCCL refuses two ranks on one device), so the self-launch path is testable on any box."""
     import torch.distributed as dist
 
-    dist.init_process_group("nccl" if torch.cuda.is_available() else "gloo")
-    t = torch.ones(1, device="cuda" if torch.cuda.is_available() else "cpu")
+    nccl = torch.cuda.device_count() >= world
+    if nccl:
+        torch.cuda.set_device(local_rank)
+    dist.init_process_group("nccl" if nccl else "gloo")
+    t = torch.ones(1, device="cuda" if nccl else "cpu")
     dist.all_reduce(t)
     if rank == 0:
         print(json.dumps({"rendezvous_ranks": int(t.item()), "world_size": dist.get_world_size()}), flush=True)
@@ -548,8 +584,15 @@ def main():
     ap.add_argument("--batch", type=int, default=None,
                     help="override the config's batch size (e.g. 7 = one rank's shard of the strong-scaling job at 8 "
                          "GPUs, to time its compute alone); not the contract's default, the line says so")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs())")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the line's other figures: resident_batch_ms, pinned_path_ms, roofline, "
+                         "strong / allreduce_ms (N > 1) and cpu_baseline")
     ap.add_argument("--rendezvous-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -559,7 +602,7 @@ def main():
     if world != args.gpus:
         sys.exit(f"bench.py: --gpus {args.gpus} but the launcher set WORLD_SIZE={world}")
     if args.rendezvous_only:
-        return rendezvous_only(world, rank)
+        return rendezvous_only(world, rank, local_rank)
     assert torch.cuda.is_available(), "bench.py needs a HIP device"
 
     from repo_amd.algorithms.repo import TIA, Dreamer, MultitaskDreamer, MultitaskRePo, RePo
@@ -599,9 +642,9 @@ def main():
         lo, hi = shard_rows(B, world, rank)
         host = tuple(np.ascontiguousarray(x[:, lo:hi]) for x in synthetic_batch(1234, B, A, image, ntasks))
         cfg.batch_size = hi - lo
-    else:
+    elif args.full:
         host = synthetic_batch(1234 + rank, B, A, image, ntasks)  # each rank holds its own B-sequence shard of the global batch
-    resident = tuple(torch.from_numpy(x).to(dev) for x in host)
+    resident = tuple(torch.from_numpy(x).to(dev) for x in host) if args.strong or args.full else None
     Bl = cfg.batch_size
 
     def run_resident(k):
@@ -643,43 +686,44 @@ def main():
 
     main_loop = run_resident if args.strong else run_from_ring
     main_loop(args.warmup)
-    from repo_amd import ops
-
-    ar = AllReduceTimer(dp) if dp is not None else None
-    top_spec, big_spec = roofline_specs((L - 1) * Bl, (H - 1) * (L - 1) * Bl)
-    timer = LaunchTimer(top_spec)
-    big_timer = timer if big_spec["label"] == top_spec["label"] else LaunchTimer(big_spec)
     import contextlib
 
+    ar = timer = big_timer = None
     with contextlib.ExitStack() as stack:
-        stack.enter_context(timer)
-        if big_timer is not timer:
-            stack.enter_context(big_timer)
+        if args.full:   # HIP events around the roofline kernels' launches and the collectives, inside the timed steps
+            ar = AllReduceTimer(dp) if dp is not None else None
+            top_spec, big_spec = roofline_specs((L - 1) * Bl, (H - 1) * (L - 1) * Bl)
+            timer = stack.enter_context(LaunchTimer(top_spec))
+            big_timer = timer if big_spec["label"] == top_spec["label"] else stack.enter_context(LaunchTimer(big_spec))
         dt = timed(main_loop, args.steps)
     if ar is not None:
         ar.stop()
-    run_resident(2)
-    dt_res = timed(run_resident, args.steps)
+    scalars = agent.last_scalars if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(agent, scalars, args.dump_outputs)
 
-    # north_star's literal input path ("sequence sampler ... pinned-memory hipMemcpyAsync'd to device"): the same loop
-    # with the HBM mirror off -- the batch is gathered on the host by repo_host_gather_rows (a few threads, into a
-    # page-locked slot) and copied on a side stream while the previous update computes
-    dt_pin = None
-    if world == 1 and not args.strong:
-        ring = agent.buffer
-        mirror, ring._mirror = ring._mirror, None
-        ring.__dict__.pop("_stage", None)
-        run_from_ring(3)
-        dt_pin = timed(run_from_ring, args.steps)
-        ring._mirror = mirror
-        ring.__dict__.pop("_stage", None)
+    dt_res = dt_pin = strong = None
+    if args.full:
+        run_resident(2)
+        dt_res = timed(run_resident, args.steps)
 
-    # N > 1: the same line also carries STRONG scaling -- one global batch of B sequences dealt 7,7,6,... over
+        # north_star's literal input path ("sequence sampler ... pinned-memory hipMemcpyAsync'd to device"): the same
+        # loop with the HBM mirror off -- the batch is gathered on the host by repo_host_gather_rows (a few threads, into
+        # a page-locked slot) and copied on a side stream while the previous update computes
+        if world == 1 and not args.strong:
+            ring = agent.buffer
+            mirror, ring._mirror = ring._mirror, None
+            ring.__dict__.pop("_stage", None)
+            run_from_ring(3)
+            dt_pin = timed(run_from_ring, args.steps)
+            ring._mirror = mirror
+            ring.__dict__.pop("_stage", None)
+
+    # N > 1: the --full line also carries STRONG scaling -- one global batch of B sequences dealt 7,7,6,... over
     # the ranks, every rank sampling its shard from its own ring (a collective-free re-shard: reset_counts()
     # on all ranks, then the first global_count() of the next update gathers the new shard sizes)
-    strong = None
     # REPO_BENCH_FORCE_STRONG=1 (with REPO_FORCE_DP=1): walk the re-shard path with one rank (the whole batch is its shard)
-    if dp is not None and (world > 1 or os.environ.get("REPO_BENCH_FORCE_STRONG") == "1") and not args.strong:
+    if args.full and dp is not None and (world > 1 or os.environ.get("REPO_BENCH_FORCE_STRONG") == "1") and not args.strong:
         from repo_amd.parallel import shard_rows
 
         lo, hi = shard_rows(B, world, rank)
@@ -733,17 +777,18 @@ def main():
                 "algorithmic_tflops": round(flop * value / 1e12, 2),
                 "frac_of_fp32_mfma_peak_all_gpus": round(flop * value / 1e12 / FP32_MFMA_PEAK_TFLOPS / nranks, 4),
             },
-            "resident_batch_ms": round(dt_res / args.steps * 1e3, 3),
-            "pinned_path_ms": round(dt_pin / args.steps * 1e3, 3) if dt_pin is not None else None,
-            "last_scalars": {k: round(float(v), 6) for k, v in agent.last_scalars.items()},
+            "last_scalars": {k: round(float(v), 6) for k, v in scalars.items()},
         }
-        line["roofline"] = roofline(timer, big_timer, (L - 1) * Bl)
-        if strong is not None:
-            line["strong"] = strong
-        if ar is not None:
-            line["allreduce_ms"] = ar.summary(args.steps)
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(B=B, A=A, algo=algo, image=image)
+        if args.full:
+            line["resident_batch_ms"] = round(dt_res / args.steps * 1e3, 3)
+            line["pinned_path_ms"] = round(dt_pin / args.steps * 1e3, 3) if dt_pin is not None else None
+            line["roofline"] = roofline(timer, big_timer, (L - 1) * Bl)
+            if strong is not None:
+                line["strong"] = strong
+            if ar is not None:
+                line["allreduce_ms"] = ar.summary(args.steps)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(B=B, A=A, algo=algo, image=image)
         print(json.dumps(line), flush=True)
     if dp is not None:
         dp.barrier()

@@ -69,7 +69,7 @@ def main():
         csvname = sys.argv[sys.argv.index("--csv-name") + 1] if "--csv-name" in sys.argv else path
         summary = {"top_by_time": top, "largest_launch": dom, "nimg": NIMG,
                    "kernel_time_sum_ms_per_update": round(tot_ns / nupd / 1e6, 3), "updates_in_trace": nupd, "csv": csvname,
-                   "source": ("rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 "
+                   "source": ("rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 "
                               f"(tools/prof_bench.sh; {nupd:.0f} updates in the trace: warm-up, timed, resident-batch and "
                               "pinned-path loops; the isolated re-runs of the timed kernels are skipped under the profiler)")}
         json.dump(summary, open(out, "w"), indent=1)
