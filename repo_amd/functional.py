@@ -116,7 +116,6 @@ def encoder_bwd(p, obs, saved, dembeds, g, accumulate=False, side=None):
 # engine.  From _DEC_COMPOSE_MIN_ROWS rows up (composing costs 1.5 GFLOP whatever the batch: the acting path's single row
 # keeps the two layers); REPO_DEC_COMPOSE=0 restores the two-layer form everywhere.
 _DEC_COMPOSE_MIN_ROWS = 512
-_DEC_PAD = 232   # 230 inputs + the bias column, padded to a multiple of 4
 
 
 def _dec_compose(rows):
@@ -124,9 +123,10 @@ def _dec_compose(rows):
 
 
 class DecHead:
-    """The composed first two decoder layers of one parameter state: w0aug (1024, 232) = [W0 | b0 | 0], w1t (3200, 1024)
-    = W1^T, w01aug (3200, 232) = W1^T w0aug = [W01 | W1^T b0 | 0], b01 (3200,)."""
-    __slots__ = ("w0aug", "w1t", "w01aug", "b01")
+    """The composed first two decoder layers of one parameter state, F = belief + state inputs (230 by default):
+    w0aug (1024, pad) = [W0 | b0 | 0], w1t (3200, 1024) = W1^T, w01aug (3200, pad) = W1^T w0aug = [W01 | W1^T b0 | 0],
+    b01 (3200,); pad = F + 1 (the bias column) rounded up to a multiple of 4 (232 at F = 230)."""
+    __slots__ = ("w0aug", "w1t", "w01aug", "b01", "pad")
 
 
 def dec_head_compose(p):
@@ -135,13 +135,21 @@ def dec_head_compose(p):
     w1 = p[2].view(p[2].shape[0], -1)                        # (1024, 3200)
     F_ = w0.shape[1]
     dh = DecHead()
-    dh.w0aug = torch.zeros(w0.shape[0], _DEC_PAD, dtype=torch.float32, device=w0.device)
+    dh.pad = (F_ + 1 + 3) // 4 * 4
+    dh.w0aug = torch.zeros(w0.shape[0], dh.pad, dtype=torch.float32, device=w0.device)
     dh.w0aug[:, :F_].copy_(w0)
     dh.w0aug[:, F_].copy_(b0)
     dh.w1t = ops.transpose(w1)                                # (3200, 1024)
-    dh.w01aug = ops.gemm(dh.w1t, dh.w0aug)                    # (3200, 232)
+    dh.w01aug = ops.gemm(dh.w1t, dh.w0aug)                    # (3200, pad)
     dh.b01 = dh.w01aug[:, F_] + p[3].repeat_interleave(w1.shape[1] // p[3].shape[0])
     return dh
+
+
+def _head_input(h0, p, feat):
+    """F = feat's width, checked against the parameters and the head's pad (its bias column is column F)."""
+    F_ = feat.shape[1]
+    assert F_ == p[0].shape[1] and h0.pad == (F_ + 1 + 3) // 4 * 4, (feat.shape, p[0].shape, h0.pad)
+    return F_
 
 
 def decoder_trunk_fwd(p, feat, head=None):
@@ -153,7 +161,7 @@ def decoder_trunk_fwd(p, feat, head=None):
     pk2, pk3 = ops.conv_up_pack(ops.DEC2, p[4]), ops.conv_up_pack(ops.DEC3, p[6])
     if _dec_compose(rows):
         h0 = head if head is not None else dec_head_compose(p)
-        F_ = feat.shape[1]
+        F_ = _head_input(h0, p, feat)
         h1 = ops.gemm(feat, h0.w01aug[:, :F_], transb=True, bias=h0.b01, epi=ops.EPI_RELU).view(rows, 128, 5, 5)
     else:
         h0 = ops.gemm(feat, p[0], transb=True, bias=p[1])
@@ -277,15 +285,15 @@ def _decoder_bwd_tail(p, feat, h0, h1, h2, d3, g, dfeat, accumulate_dfeat, accum
     w1 = p[2].view(p[2].shape[0], -1)
     if isinstance(h0, DecHead):
         # the first two layers ran composed (decoder_trunk_fwd): every gradient of the pair through (G | s) = d1^T (feat | 1)
-        F_ = feat.shape[1]
-        gaug = torch.zeros(d1f.shape[1], _DEC_PAD, dtype=torch.float32, device=d1f.device)     # (3200, 232) = [G | s | 0]
+        F_ = _head_input(h0, p, feat)
+        gaug = torch.zeros(d1f.shape[1], h0.pad, dtype=torch.float32, device=d1f.device)       # (3200, pad) = [G | s | 0]
         _, s_ = ops.gemm_wgrad(d1f, feat, dW=gaug[:, :F_])
         gaug[:, F_].copy_(s_)
 
         def wpair():
             ops.gemm(h0.w0aug, gaug, transb=True, out=g[2].view(w1.shape), accumulate=accumulate)   # d W1 = W0 G^T + b0 s^T
             ops.channel_sum(d1.view(rows, 128, 25), out=g[3], accumulate=accumulate)
-            d0aug, _ = ops.gemm_wgrad(h0.w1t, gaug, want_bias=False)                                # (1024, 232) = [W1 G | W1 s | 0]
+            d0aug, _ = ops.gemm_wgrad(h0.w1t, gaug, want_bias=False)                                # (1024, pad) = [W1 G | W1 s | 0]
             if accumulate:
                 g[0].add_(d0aug[:, :F_])
                 g[1].add_(d0aug[:, F_])
@@ -296,7 +304,7 @@ def _decoder_bwd_tail(p, feat, h0, h1, h2, d3, g, dfeat, accumulate_dfeat, accum
         fk.run(wpair)
         if dfeat is not None:
             # d feat = d1 W01, as an NT product over W01^T (a 3 MB transposing copy: 94 -> ~55 us at 2450 rows)
-            w01t = ops.transpose(h0.w01aug)                                                         # (232, 3200)
+            w01t = ops.transpose(h0.w01aug)                                                         # (pad, 3200)
             ops.gemm(d1f, w01t[:F_], transb=True, out=dfeat, accumulate=accumulate_dfeat)
         fk.join()
         return

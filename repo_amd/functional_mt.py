@@ -20,7 +20,7 @@ import torch
 
 from . import ops
 from .algorithms.repo.models.conditional import DEC_CHANNELS, ENC_CHANNELS, film_offsets
-from .functional import DecHead, _DEC_PAD, _Fork, _dec_compose, dec_head_compose
+from .functional import DecHead, _Fork, _dec_compose, _head_input, dec_head_compose
 
 _ENC_L = (ops.ENC1, ops.ENC2, ops.ENC3, ops.ENC4)
 _ENC_OFF = film_offsets(ENC_CHANNELS)
@@ -100,7 +100,8 @@ def _cond_decoder_trunk(p, feat, cond, head=None):
         # output element, one FiLM pair per 25 of them (bias_div = -25)
         tabs = ops.film_tables(film, DEC_CHANNELS)
         h0 = head if head is not None else dec_head_compose(p)
-        h1 = ops.gemm(feat, h0.w01aug[:, : feat.shape[1]], transb=True, bias=h0.b01, bias_div=-25, epi=ops.EPI_FILM_RELU,
+        F_ = _head_input(h0, p, feat)
+        h1 = ops.gemm(feat, h0.w01aug[:, :F_], transb=True, bias=h0.b01, bias_div=-25, epi=ops.EPI_FILM_RELU,
                       aux=tabs[0].view(rows, -1)).view(rows, 128, 5, 5)
         h2 = ops.conv_up(ops.DEC2, h1, p[4], p[5], epi=ops.EPI_FILM_RELU, aux=tabs[1], pack=pk2)
         h3 = ops.conv_up(ops.DEC3, h2, p[6], p[7], epi=ops.EPI_FILM_RELU, aux=tabs[2], pack=pk3)
@@ -156,7 +157,7 @@ def cond_decoder_bwd(p, feat, cond, saved, g, dfeat=None, accumulate_dfeat=False
         return ops.film_bwd(dh, ys[l], film, *_DEC_OFF[l], dfilm)
 
     composed = isinstance(h0, DecHead)
-    w01t = ops.transpose(h0.w01aug) if composed else None   # (232, 3200): W01^T, for the exact FiLM pass and d feat
+    w01t = ops.transpose(h0.w01aug) if composed else None   # (pad, 3200): W01^T, for the exact FiLM pass and d feat
     fk = _Fork(side)
     dfilm = torch.empty_like(film)
 
@@ -188,8 +189,8 @@ def cond_decoder_bwd(p, feat, cond, saved, g, dfeat=None, accumulate_dfeat=False
     d1f = dy1.view(rows, 128 * 25)
     w1 = p[2].view(p[2].shape[0], -1)
     if composed:   # functional._decoder_bwd_tail's composed branch: every gradient of the pair through (G | s) = d y1^T (feat | 1)
-        F_ = feat.shape[1]
-        gaug = torch.zeros(d1f.shape[1], _DEC_PAD, dtype=torch.float32, device=d1f.device)
+        F_ = _head_input(h0, p, feat)
+        gaug = torch.zeros(d1f.shape[1], h0.pad, dtype=torch.float32, device=d1f.device)
         _, s_ = ops.gemm_wgrad(d1f, feat, dW=gaug[:, :F_])
         gaug[:, F_].copy_(s_)
 

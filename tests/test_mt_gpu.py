@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 from oracle import fixtures as fx
 from oracle import repo_oracle as ro
-from tests.test_update_gpu import Env, Logger, dev_batch, dev_noise
+from tests.test_update_gpu import Env, Logger, dev_batch, dev_noise, grad_snapshots, module_grad_norms
 from tests.util import l2err, log, relerr
 
 pytestmark = pytest.mark.gpu
@@ -318,8 +318,16 @@ def test_mt_update_matches_reference_goldens(golden_dir, fname, algo):
         batch, _ = dev_batch(L, B, A, 11 + u, u8=(u % 2 == 0))
         tasks, _ = dev_tasks(L, B, C, 11 + u)
         agent.noise_source, _ = dev_noise(L, B, H, A, 101 + u)
-        beliefs, post = agent.train_dynamics(tasks, batch[0], batch[1], batch[2], 1.0 - batch[3])
-        agent.train_actor_critic(tasks[1:].flatten(0, 1), beliefs.flatten(0, 1), post.flatten(0, 1))
+        with grad_snapshots(agent) as snap:
+            beliefs, post = agent.train_dynamics(tasks, batch[0], batch[1], batch[2], 1.0 - batch[3])
+            agent.train_actor_critic(tasks[1:].flatten(0, 1), beliefs.flatten(0, 1), post.flatten(0, 1))
+        # per-module pre-clip gradient norms: 2e-3 (the totals' bound) for RePo, 1e-2 (the CPU oracle's own bound against
+        # the reference's goldens, tests/test_oracle_golden.py) for Dreamer's attached decoder
+        mtol = 2e-3 if algo == "repo_multitask" else 1e-2
+        for mod, got, w in zip(fx.MODULES, module_grad_norms(agent, snap), g[f"u{u}/module_grad_norms"]):
+            r = abs(got - w) / w
+            log(f"[{fname}] update {u} module grad-norm {mod}: got {got:.6g} ref {w:.6g} rel {r:.2e}")
+            assert r < mtol, (fname, u, mod, got, w)
         scal = agent.last_scalars
         assert sorted(scal) == keys, (sorted(scal), keys)
         atol = 1e-4 if u == 0 else 2e-3
@@ -342,12 +350,19 @@ def test_mt_update_matches_reference_goldens(golden_dir, fname, algo):
         assert abs(sums[n] - s_) <= 1e-3 * abs(a_) + 1e-7, (n, sums[n], s_)
 
 
-@pytest.mark.parametrize("algo,A", [("dreamer_multitask", 6), ("repo_multitask", 6), ("repo_multitask", 2)])
-def test_mt_update_matches_oracle_grads(algo, A):
+@pytest.mark.parametrize("algo,A,LB", [
+    pytest.param("dreamer_multitask", 6, (9, 5), id="dreamer_multitask-6"),
+    pytest.param("repo_multitask", 6, (9, 5), id="repo_multitask-6"),
+    pytest.param("repo_multitask", 2, (9, 5), id="repo_multitask-2"),
+    pytest.param("dreamer_multitask", 6, (33, 16), id="dreamer_multitask-6-512rows"),
+])
+def test_mt_update_matches_oracle_grads(algo, A, LB):
     """Flat pre-clip gradients of the three optimisers against the oracle's autograd, per module too (the FiLM layers'
     and the condition columns' gradients vanish in the flat norm), with the KL term active.  A = 2: the action size of
-    two of the reference's three multitask suites (the rollout then runs on the per-step engine)."""
-    L, B, H, C = 9, 5, 5, 3
+    two of the reference's three multitask suites (the rollout then runs on the per-step engine).  (L - 1) * B = 512:
+    the decoder's composed head (functional._DEC_COMPOSE_MIN_ROWS), with its input gradient (Dreamer's attached
+    decoder)."""
+    (L, B), H, C = LB, 5, 3
     over = dict(init_beta=0.05, target_kl=0.3, beta_lr=1e-2, free_nats=0.1)
     agent, cfg = make_mt(algo, L, B, H, A, C, **over)
     oracle = ro.OracleMultitask(cfg, A, C, seed=7)
@@ -386,6 +401,7 @@ def test_mt_update_matches_oracle_grads(algo, A):
             for o, p, gr, q in zip(opt.offsets, opt.params, ograds, oparams):
                 a = snap[name][o : o + p.numel()].cpu()
                 em = ((a - gr.reshape(-1)).norm() / (gr.norm() + 1e-12)).item()
+                log(f"[oracle {algo} L={L} B={B}] update {u} per-tensor {name} {tuple(p.shape)}: l2 rel {em:.2e}")
                 assert em < 5e-3, (name, tuple(p.shape), em)
         if algo == "repo_multitask":
             np.testing.assert_allclose(agent.log_beta.cpu().numpy(), oracle.log_beta.detach().numpy(), atol=1e-5)

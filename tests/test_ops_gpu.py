@@ -726,3 +726,219 @@ def test_device_check_and_arch_guard():
     assert L.repo_device_check(torch.cuda.device_count()) == -1  # REPO_E_BADARG
     assert L.repo_strerror(-5).decode() == "device is not gfx950"
     assert "gfx950" in torch.cuda.get_device_properties(0).gcnArchName
+
+
+# ----------------------------------------------------------------------------- the decoder through its composed head
+# From functional._DEC_COMPOSE_MIN_ROWS rows up the decoder's fc1 and its 1x1 -> 5x5 transposed conv1 run as ONE layer
+# (functional.dec_head_compose: W01 = W1^T W0, its bias column padded to DecHead.pad) and their gradients come out of
+# (G | s) = d1^T (feat | 1).  These tests run the whole decoder at composing row counts and latent widths against the
+# reference's TWO-layer form (oracle/repo_oracle.py: decoder_fwd / cond_decoder_fwd) in float64, tensor by tensor, with
+# the same shapes under REPO_DEC_COMPOSE=0 so that both forms stay pinned.
+def _dec64(P, feat, gates=None, film=None):
+    """float64 restatement of oracle decoder_fwd (film = (gammas, betas): cond_decoder_fwd) -> (fc1 output, [h1, h2, ...],
+    output layer).  gates: None (ReLU), or one fixed 0/1 tensor per ReLU -- the GPU forward's own `h > 0` -- so that a
+    pre-activation within rounding of zero takes the GPU's side of the ReLU in the backward."""
+    rows = feat.shape[0]
+    h0 = F.linear(feat, P["fc1.weight"], P["fc1.bias"])
+    x = h0.view(rows, -1, 1, 1)
+    convs = [k[: -len(".weight")] for k in P if k.startswith("conv") and k.endswith(".weight")]
+    hs = []
+    for i, name in enumerate(convs[:-1]):
+        pre = F.conv_transpose2d(x, P[f"{name}.weight"], P[f"{name}.bias"], stride=2)
+        if film is not None:
+            pre = (1 + film[0][i][..., None, None]) * pre + film[1][i][..., None, None]
+        x = F.relu(pre) if gates is None else pre * gates[i]
+        hs.append(x)
+    return h0, hs, F.conv_transpose2d(x, P[f"{convs[-1]}.weight"], P[f"{convs[-1]}.bias"], stride=2)
+
+
+def _dec_case_params(F_, image, tia, seed):
+    from oracle import fixtures as fx
+
+    # fc1 is F_ = belief + state wide; the remaining modules are drawn too (make_params' order) and not used here
+    return fx.make_params(6, seed, image=image, tia=tia, belief=F_ - 30, state=30)["obs_model"]
+
+
+def _dec_frames(rs, rows, image):
+    u8 = torch.from_numpy(rs.randint(0, 256, size=(rows, 3, image, image)).astype(np.uint8))
+    return u8, (u8.double() / 255) * 2 - 1
+
+
+DEC_CASES = [
+    # (rows, F = belief + state, stack): 511 stays two-layer, 512 is the first composing row count, 637 a data-parallel
+    # shard's, 2450 the headline update's; F 229 / 231: odd K into the padded leading dimension; 232 / 264: a pad past 232
+    (511, 230, "64"), (512, 230, "64"), (637, 230, "64"), (2450, 230, "64"),
+    (512, 130, "64"), (512, 229, "64"), (512, 231, "64"), (512, 232, "64"), (512, 264, "64"),
+    (512, 230, "128"),   # the build-defined 128 x 128 stack (12 tensors: functional._decoder_bwd_128)
+    (512, 230, "tia"),   # TIA's 6-channel output layer (T_DEC4; decoder_fwd + an outside cotangent, as tia.py runs it)
+]
+
+
+@pytest.mark.parametrize("compose", ["1", "0"])
+@pytest.mark.parametrize("rows,F_,stack", DEC_CASES)
+def test_decoder_matches_fp64_two_layer_form_per_tensor(ops, monkeypatch, rows, F_, stack, compose):
+    """Fn.decoder_fwd(_nll) / Fn.decoder_bwd against fp64 autograd of the two-layer decoder: every activation, the
+    output, the NLL and its gradient, each of the ten (twelve) parameter gradients and d feat, each within TOL; then the
+    same backward accumulating into pre-filled gradients, on a side stream (RePo's call) and deferred (Dreamer's call) --
+    the last two bit-identical to the serial run."""
+    import repo_amd.functional as Fn
+
+    monkeypatch.setenv("REPO_DEC_COMPOSE", compose)
+    image, tia = (128 if stack == "128" else 64), stack == "tia"
+    rs = np.random.RandomState(rows + 7 * F_ + len(stack))
+    P = _dec_case_params(F_, image, tia, seed=rows + F_)
+    p = [dev(torch.from_numpy(v)) for v in P.values()]
+    feat = rnd(rs, rows, F_, scale=0.7)
+    u8, tgt = _dec_frames(rs, rows, image)
+    gs = 1.0 / rows
+    # -- forward (the GPU's), then the engagement of the composed head
+    if tia:
+        out, saved = Fn.decoder_fwd(p, dev(feat))
+        cot = rnd(rs, *out.shape, scale=gs)
+        saved = (*saved, dev(cot))
+    else:
+        loss, saved = Fn.decoder_fwd_nll(p, dev(feat), dev(u8), gs)
+        out, _ = Fn.decoder_fwd(p, dev(feat))
+    composed = isinstance(saved[0], Fn.DecHead)
+    assert composed == (rows >= 512 and compose == "1"), (rows, compose, type(saved[0]))
+    nrelu = 4 if image == 128 else 3
+    hs_gpu = saved[1 : 1 + nrelu]
+    # -- fp64: the plain forward (values), then the gated one (gradients)
+    P64 = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in P.items()}
+    feat64 = feat.double().requires_grad_(True)
+    errs = {}
+    with torch.no_grad():
+        h0w, hsw, outw = _dec64(P64, feat64)
+    if not composed:
+        errs["h0"] = relerr(saved[0], h0w)
+    for i, (hg, hw) in enumerate(zip(hs_gpu, hsw), 1):
+        errs[f"h{i}"] = relerr(hg, hw)
+    errs["out"] = relerr(out, outw)
+    if not tia:
+        d = outw - tgt
+        want_loss = (0.5 * d * d).sum().item()
+        errs["nll"] = abs(loss.item() - want_loss) / want_loss
+        errs["dpre"] = relerr(saved[4] if image == 64 else saved[5], d * gs)
+    del h0w, hsw, outw
+    gates = [(h > 0).double().cpu() for h in hs_gpu]
+    _, _, out64 = _dec64(P64, feat64, gates=gates)
+    if tia:
+        (out64 * cot.double()).sum().backward()
+    else:
+        (0.5 * gs * (out64 - tgt).pow(2)).sum().backward()
+    del out64, gates
+    names = list(P)
+    wants = [P64[k].grad for k in names] + [feat64.grad]
+
+    def bwd(**kw):
+        g = [torch.empty_like(t) for t in p]
+        dfeat = torch.empty(rows, F_, device="cuda")
+        Fn.decoder_bwd(p, dev(feat), saved, g, dfeat=dfeat, **kw)
+        return g + [dfeat]
+
+    got = bwd()
+    torch.cuda.synchronize()
+    for k, a, w in zip(names + ["dfeat"], got, wants):
+        errs[f"d {k}"] = relerr(a, w)
+    log(f"decoder {stack} rows={rows} F={F_} compose={compose} (composed {composed}): "
+        + " ".join(f"{k} {e:.2e}" for k, e in errs.items()))
+    bad = {k: e for k, e in errs.items() if e >= TOL}
+    assert not bad, bad
+    # accumulate into pre-filled gradients (and d feat): want + prefill
+    pre = [dev(rnd(rs, *w.shape, scale=0.5 * float(w.abs().max()))) for w in wants]
+    g = [t.clone() for t in pre[:-1]]
+    dfeat = pre[-1].clone()
+    Fn.decoder_bwd(p, dev(feat), saved, g, dfeat=dfeat, accumulate=True, accumulate_dfeat=True)
+    for k, a, w, b in zip(names + ["dfeat"], g + [dfeat], wants, pre):
+        e = relerr(a, w + b.double().cpu())
+        assert e < TOL, ("accumulate", k, e)
+    # RePo's call (weight gradients on a side stream) and Dreamer's (deferred closures): the serial run's bits
+    side = torch.cuda.Stream()
+    assert all(torch.equal(a, b) for a, b in zip(bwd(side=side), got)), "side stream"
+    closures = []
+    res = bwd(deferred=closures)
+    assert closures, "nothing was deferred"
+    for fn in closures:
+        fn()
+    assert all(torch.equal(a, b) for a, b in zip(res, got)), "deferred"
+
+
+@pytest.mark.parametrize("compose", ["1", "0"])
+@pytest.mark.parametrize("F_", [230, 232])
+def test_cond_decoder_matches_fp64_two_layer_form_per_tensor(ops, monkeypatch, F_, compose):
+    """The multitask decoder (Fm.cond_decoder_fwd_nll / cond_decoder_bwd: FiLM on conv1..conv3) at 512 rows against fp64
+    autograd of oracle cond_decoder_fwd, tensor by tensor (twelve parameter gradients incl. the FiLM pair, and d feat into
+    a strided view, as dreamer_mt.py writes it).  Task 0 gates one conv1 plane off (1 + gamma = 0 up to rounding, beta > 0:
+    the plane is active) and task 1 another to 1 + gamma = 1e-4: the composed head's exact FiLM pass (FILM_DENSE over W01^T
+    with one bias per output element) must recover both planes' gamma gradients; task 2 does the same to a conv2 plane."""
+    import repo_amd.functional as Fn
+    import repo_amd.functional_mt as Fm
+    from oracle import fixtures as fx
+    from oracle import repo_oracle as ro
+
+    monkeypatch.setenv("REPO_DEC_COMPOSE", compose)
+    rows, C = 512, 3
+    rs = np.random.RandomState(F_ + 31)
+    P = fx.make_params(6, 7, cond=C, belief=F_ - 30, state=30)["obs_model"]
+    fw, fb = P["film.weight"], P["film.bias"]
+    tot = 128 + 64 + 32
+    for task, ch, one_plus_gamma in ((0, 5, 0.0), (1, 77, 1e-4), (2, 128 + 9, 0.0)):
+        fw[ch, task] = np.float32(-1.0 + one_plus_gamma) - fb[ch]
+        fw[tot + ch, task] = np.float32(0.5) - fb[tot + ch]
+    p = [dev(torch.from_numpy(v)) for v in P.values()]
+    feat = rnd(rs, rows, F_, scale=0.7)
+    cond = torch.from_numpy(np.eye(C, dtype=np.float32)[rs.randint(0, C, size=rows)])
+    u8, tgt = _dec_frames(rs, rows, 64)
+    gs = 1.0 / rows
+    loss, saved = Fm.cond_decoder_fwd_nll(p, dev(feat), dev(cond), dev(u8), gs)
+    out, _ = Fm.cond_decoder_fwd(p, dev(feat), dev(cond))
+    composed = isinstance(saved[1], Fn.DecHead)
+    assert composed == (compose == "1"), (compose, type(saved[1]))
+    gam = saved[0][:, :tot].cpu()
+    assert float((1 + gam[:, 5]).abs().min()) < 1e-6 and float((1 + gam[:, 77]).abs().min()) < 2e-4
+    assert float((1 + gam[:, 128 + 9]).abs().min()) < 1e-6
+    hs_gpu = saved[3]
+    P64 = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in P.items()}
+    feat64 = feat.double().requires_grad_(True)
+    errs = {}
+    with torch.no_grad():
+        _, hsw, outw = _dec64(P64, feat64, film=ro._film(P64, cond.double(), (128, 64, 32)))
+    for i, (hg, hw) in enumerate(zip(hs_gpu, hsw), 1):
+        errs[f"h{i}"] = relerr(hg, hw)
+    errs["out"] = relerr(out, outw)
+    d = outw - tgt
+    want_loss = (0.5 * d * d).sum().item()
+    errs["nll"] = abs(loss.item() - want_loss) / want_loss
+    errs["dpre"] = relerr(saved[4], d * gs)
+    del hsw, outw, d
+    gates = [(h > 0).double().cpu() for h in hs_gpu]
+    _, _, out64 = _dec64(P64, feat64, gates=gates, film=ro._film(P64, cond.double(), (128, 64, 32)))
+    (0.5 * gs * (out64 - tgt).pow(2)).sum().backward()
+    del out64, gates
+    names = list(P)
+    wants = [P64[k].grad for k in names] + [feat64.grad]
+    ld = F_ + C + 1   # d feat lands in the first F_ columns of a wider row (dreamer_mt.py: [belief | state | task])
+
+    def bwd(accumulate=False, side=None, fill=None):
+        g = [torch.empty_like(t) for t in p] if fill is None else [t.clone() for t in fill[:-1]]
+        buf = torch.full((rows, ld), 7.0, device="cuda")
+        if fill is not None:
+            buf[:, :F_] = fill[-1]
+        Fm.cond_decoder_bwd(p, dev(feat), dev(cond), saved, g, dfeat=buf[:, :F_], accumulate_dfeat=fill is not None,
+                            accumulate=accumulate, side=side)
+        assert bool((buf[:, F_:] == 7.0).all()), "d feat wrote past its columns"
+        return g + [buf[:, :F_]]
+
+    got = bwd()
+    torch.cuda.synchronize()
+    for k, a, w in zip(names + ["dfeat"], got, wants):
+        errs[f"d {k}"] = relerr(a, w)
+    log(f"cond decoder rows={rows} F={F_} compose={compose} (composed {composed}): "
+        + " ".join(f"{k} {e:.2e}" for k, e in errs.items()))
+    bad = {k: e for k, e in errs.items() if e >= TOL}
+    assert not bad, bad
+    pre = [dev(rnd(rs, *w.shape, scale=0.5 * float(w.abs().max()))) for w in wants]
+    for k, a, w, b in zip(names + ["dfeat"], bwd(accumulate=True, fill=pre), wants, pre):
+        e = relerr(a, w + b.double().cpu())
+        assert e < TOL, ("accumulate", k, e)
+    assert all(torch.equal(a, b) for a, b in zip(bwd(side=torch.cuda.Stream()), got)), "side stream"
