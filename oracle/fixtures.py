@@ -187,16 +187,17 @@ def param_shapes(action_size, belief=200, state=30, hidden=200, embed=1024, imag
     return out
 
 
-def make_params(action_size, seed=7, image=64, tia=False, cond=0, belief=200, state=30):
+def make_params(action_size, seed=7, image=64, tia=False, cond=0, belief=200, state=30, hidden=200):
     """{module: OrderedDict(name -> float32 ndarray)}; uniform(-k, k), k = fan_in**-0.5.
-    belief / state: the latent widths (cfg.belief_size / state_size); the defaults draw the golden recipe's parameters.
+    belief / state / hidden: the latent and hidden widths (cfg.belief_size / state_size / hidden_size); the defaults draw
+    the golden recipe's parameters.
 
     One RandomState drawn sequentially in (module, state_dict) order; a bias uses
     the bound of the weight registered just before it (rnn.bias_* use weight_hh's).
     """
     rs = np.random.RandomState(seed)
     out = OrderedDict()
-    for mod, shapes in param_shapes(action_size, belief=belief, state=state, image=image, tia=tia, cond=cond).items():
+    for mod, shapes in param_shapes(action_size, belief=belief, state=state, hidden=hidden, image=image, tia=tia, cond=cond).items():
         d = OrderedDict()
         k = 1.0
         for name, shp in shapes.items():

@@ -39,6 +39,7 @@ from . import fixtures as fx
 
 LOG_2PI = math.log(2.0 * math.pi)
 ATANH_CLAMP = 0.99999997  # literal of models/utils.py:128 (rounds to 0.99999994 in fp32)
+ATANH_CLAMP_F32 = float(np.float32(ATANH_CLAMP))  # the bound the reference applies (its tensors are fp32); a float64 run keeps it
 
 
 # --------------------------------------------------------------------------- modules
@@ -147,7 +148,7 @@ def tanh_normal_log_prob(y, mean, std):
     """log-prob of y under tanh(Normal(mean,std)), summed over the action dim.
     models/utils.py:126-134 (inverse recomputed from y, clamped) + torch's
     TransformedDistribution.log_prob / Normal.log_prob."""
-    yc = torch.where(y.abs() <= 1.0, torch.clamp(y, -ATANH_CLAMP, ATANH_CLAMP), y)
+    yc = torch.where(y.abs() <= 1.0, torch.clamp(y, -ATANH_CLAMP_F32, ATANH_CLAMP_F32), y)
     x = torch.atanh(yc)
     ladj = 2.0 * (math.log(2.0) - x - F.softplus(-2.0 * x))
     base = -((x - mean) ** 2) / (2 * std**2) - std.log() - 0.5 * LOG_2PI
@@ -155,8 +156,14 @@ def tanh_normal_log_prob(y, mean, std):
 
 
 def tanh_normal_entropy(mean, std, eps):
-    """SampleDist.entropy (models/utils.py:160-163): eps is (samples, rows, A)."""
-    y = torch.tanh(mean + std * eps)
+    """SampleDist.entropy (models/utils.py:160-163): eps is (samples, rows, A).
+    The reference forms u = mean + std * eps and the sample y = tanh(u) as fp32 values and recomputes atanh from y (near
+    |y| = 1 one ulp of y moves atanh by up to 0.35); a float64 run keeps those rounding points (the casts are exact for
+    float32 inputs).  torch's tanh backward reads its (rounded) output: dy/du = 1 - y^2, which then cancels atanh's
+    1 / (1 - y^2) exactly inside the clamp; the float64 path keeps that too."""
+    u = (mean + std * eps).float().to(mean.dtype)
+    y = torch.tanh(u.detach()).float().to(mean.dtype)
+    y = y + (1 - y * y) * (u - u.detach())
     return -tanh_normal_log_prob(y, mean, std).mean(0)
 
 

@@ -16,6 +16,7 @@ namespace repo {
 
 // ------------------------------------------------------------------ element-wise kernels
 // raw (rows,2A) -> mean = ms*tanh(raw_m/ms), std = softplus(raw_s + init) + min_std
+// (libm tanhf: 1 - 2 / (exp(2x) + 1) loses the relative accuracy of small means -- 1e-5 of the largest at A = 1)
 // if eps: action = tanh(mean + std*eps), xsa[row] = [state(row), action]
 __global__ void actor_head_fwd_kernel(int rows, int A, int S, const float* __restrict__ raw,
                                       const float* __restrict__ eps, const float* __restrict__ state, int ldstate,
@@ -30,15 +31,15 @@ __global__ void actor_head_fwd_kernel(int rows, int A, int S, const float* __res
         xsa[(size_t)row * ldx + k] = state[(size_t)row * ldstate + k];
       } else {
         const int a = k - S;
-        const float mu = mean_scale * tanh_fast(raw[(size_t)row * 2 * A + a] / mean_scale);
+        const float mu = mean_scale * tanhf(raw[(size_t)row * 2 * A + a] / mean_scale);
         const float sd = softplus(raw[(size_t)row * 2 * A + A + a] + init_std) + min_std;
         mean[(size_t)row * A + a] = mu;
         stdv[(size_t)row * A + a] = sd;
-        xsa[(size_t)row * ldx + k] = tanh_fast(fmaf(sd, eps[(size_t)row * A + a], mu));
+        xsa[(size_t)row * ldx + k] = tanhf(fmaf(sd, eps[(size_t)row * A + a], mu));
       }
     } else {
       const int row = i / A, a = i % A;
-      mean[i] = mean_scale * tanh_fast(raw[(size_t)row * 2 * A + a] / mean_scale);
+      mean[i] = mean_scale * tanhf(raw[(size_t)row * 2 * A + a] / mean_scale);
       stdv[i] = softplus(raw[(size_t)row * 2 * A + A + a] + init_std) + min_std;
     }
   }

@@ -73,6 +73,9 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
   const __amdgpu_buffer_rsrc_t q_gates = wrsrc(p.gates, p.gates_bytes);
   const int xf = xfrag32(lane);
   const int c0 = wave * 32 + 4 * lh;  // first column of this lane's quad 0 in a layer tile
+  // a gate row is [r | z | n | gh_n], each D wide: a quad at column >= D is columns 0..3 of the NEXT block, so the gate
+  // stores (and the new belief's) are guarded per lane on c0 + 8 i < D -- a per-wave guard let the lh = 1 lanes of the
+  // last tile overwrite z, n, gh_n and the next row's r whenever D % 8 == 4
   const unsigned gvoff = li < nr ? 4u * ((unsigned)(r0 + li) * 4u * (unsigned)D + (unsigned)c0) : 0x80000000u;
 
   for (int i = tid; i < lds_bytes / 16; i += 512) reinterpret_cast<f32x4v*>(lds32)[i] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -213,7 +216,7 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = sigmoidf(v[r]);
           set_quad(rg, i, v);
-          if (wave * 32 + 8 * i < D)
+          if (c0 + 8 * i < D)
             GST32(__builtin_bit_cast(u32x4v, v), q_gates, gvoff + 32u * i, gs, 0);
         }
       }
@@ -233,7 +236,7 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) ng[r] = tanh_fast(ng[r] + r_[r] * gh[r]);
           set_quad(gin, i, ng);
-          if (wave * 32 + 8 * i < D) {
+          if (c0 + 8 * i < D) {
             GST32(__builtin_bit_cast(u32x4v, gh), q_gates, gvoff + 32u * i,
                                                    gs + 12u * D, 0);
             GST32(__builtin_bit_cast(u32x4v, ng), q_gates, gvoff + 32u * i,
@@ -247,7 +250,7 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
         wrun32<2 * BW, kPD32, BW>(az, HA + xf, psH, wb, rw, Fp + xf, psF);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          if (wave * 32 + 8 * i < D) {
+          if (c0 + 8 * i < D) {
             f32x4v zg = quad(az, i);
 #pragma unroll
             for (int r = 0; r < 4; ++r) zg[r] = sigmoidf(zg[r]);
@@ -267,7 +270,7 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
     if (gact) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        if (wave * 32 + 8 * i < D) stq32(Fp, psF, c0 + 8 * i, li, quad(hnew, i));
+        if (c0 + 8 * i < D) stq32(Fp, psF, c0 + 8 * i, li, quad(hnew, i));
     }
     lds_barrier();
     save_tile(Fp, psF, D, p.featx, (unsigned)F, tN + N);  // the new belief: columns [0, D) of featx[t + 1]

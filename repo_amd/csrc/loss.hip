@@ -25,7 +25,7 @@ __global__ void final_sum_kernel(const float* __restrict__ parts, int n, int nva
 // mode 0 (RePo, repo.py:64-83): out = sum_rows KL_row; gradients of
 //   beta * (alpha * KL(sg q || p) + (1-alpha) * KL(q || sg p)) * scale
 // mode 1 (Dreamer, dreamer.py:278-282): out = sum_rows max(KL_row, free_nats); gradients of
-//   max(KL_row, free_nats) * scale on both sides.
+//   max(KL_row, free_nats) * scale on both sides (half of them for a row whose KL equals free_nats).
 // One wave per row (S <= 64 lanes active).
 __global__ __launch_bounds__(256) void kl_kernel(int rows, int S, const float* __restrict__ pm,
                                                  const float* __restrict__ ps, const float* __restrict__ qm,
@@ -60,8 +60,9 @@ __global__ __launch_bounds__(256) void kl_kernel(int rows, int S, const float* _
       wq = beta * (1.f - alpha) * scale;
       if (lane == 0) acc += klrow;
     } else {
+      // torch.max(kl, free_nats) is torch.maximum: at a tie each side receives half the gradient
       const bool active = klrow > free_nats;
-      wp = wq = active ? scale : 0.f;
+      wp = wq = active ? scale : klrow == free_nats ? 0.5f * scale : 0.f;
       if (lane == 0) acc += active ? klrow : free_nats;
     }
     if (lane < S) {

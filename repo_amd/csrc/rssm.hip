@@ -1094,7 +1094,9 @@ extern "C" int repo_rssm_observe_bwd(int64_t T, int64_t B, int64_t A, int64_t D,
   a.dfeat = dfeat; a.dprior_state = dprior_state; a.dpm = dpm; a.dps = dps; a.dqm = dqm; a.dqs = dqs;
   a.doutp = doutp; a.doutq = doutq; a.dhp = dhp; a.dhq = dhq; a.dgi = dgi; a.dgh = dgh; a.de = de;
   a.dprev_belief = dprev_belief; a.dprev_state = dprev_state; a.min_std = min_std;
-  if (B >= 512) {
+  // the output-delta role takes one thread per (row, 2S column): R * 2S <= blockDim.  Four rows on 256 threads hold
+  // S <= 32 only; wider states (up to 64) take two rows on 512
+  if (B >= 512 && 4 * 2 * S <= 256) {
     hipLaunchKernelGGL((observe_bwd_kernel<4, 1>), dim3(cdiv(B, 4)), dim3(256), 0, stream, a);
   } else if (B >= 128) {
     hipLaunchKernelGGL((observe_bwd_kernel<2, 2>), dim3(cdiv(B, 2)), dim3(512), 0, stream, a);

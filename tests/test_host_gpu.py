@@ -182,17 +182,28 @@ def test_train_agent_runs_from_buffer():
 
 def test_acting_path_matches_oracle():
     """update_latent_and_select_action (dreamer.py:175-196): one filtering step + rsample / mode."""
-    A = 6
-    agent, cfg = make_agent("repo", 8, 4, 5, A)
-    o = ro.OracleAgent(cfg, A, seed=7)
+    _acting_path_matches_oracle(6)
+
+
+@pytest.mark.parametrize("belief,hidden,state,A", [pytest.param(200, 200, 30, 1, id="cartpole"),
+                                                   pytest.param(208, 208, 32, 16, id="full-blocks")])
+def test_acting_path_at_other_widths_matches_oracle(belief, hidden, state, A):
+    """The same at widths whose scan / head engines differ from the default's (tests/test_widths_gpu.py)."""
+    _acting_path_matches_oracle(A, belief, hidden, state)
+
+
+def _acting_path_matches_oracle(A, belief=200, hidden=200, state=30):
+    D, S = belief, state
+    agent, cfg = make_agent("repo", 8, 4, 5, A, belief_size=belief, hidden_size=hidden, state_size=state)
+    o = ro.OracleAgent(cfg, A, params=fx.make_params(A, 7, belief=belief, state=state, hidden=hidden))
     rs = np.random.RandomState(5)
     obs_u8 = rs.randint(0, 256, (1, 3, 64, 64)).astype(np.uint8)
     obs = torch.from_numpy(fx.preprocess_u8(obs_u8))
-    belief = torch.from_numpy(rs.standard_normal((1, 200)).astype(np.float32) * 0.3)
-    state = torch.from_numpy(rs.standard_normal((1, 30)).astype(np.float32))
+    belief = torch.from_numpy(rs.standard_normal((1, D)).astype(np.float32) * 0.3)
+    state = torch.from_numpy(rs.standard_normal((1, S)).astype(np.float32))
     action = torch.from_numpy(rs.uniform(-1, 1, (1, A)).astype(np.float32))
-    e1 = torch.from_numpy(rs.standard_normal((1, 1, 30)).astype(np.float32))
-    e2 = torch.from_numpy(rs.standard_normal((1, 1, 30)).astype(np.float32))
+    e1 = torch.from_numpy(rs.standard_normal((1, 1, S)).astype(np.float32))
+    e2 = torch.from_numpy(rs.standard_normal((1, 1, S)).astype(np.float32))
     ea = torch.from_numpy(rs.standard_normal((1, A)).astype(np.float32))
     es = torch.from_numpy(rs.standard_normal((100, 1, A)).astype(np.float32))
     with torch.no_grad():
@@ -217,7 +228,7 @@ def test_acting_path_matches_oracle():
     np.testing.assert_allclose(a_mode.cpu().numpy(), want_mode.numpy(), rtol=1e-4, atol=1e-5)
     # full method (draws its own noise): shapes, range, determinism of the belief path
     b2, s2, a2 = agent.update_latent_and_select_action(belief.cuda(), state.cuda(), action.cuda(), obs.cuda(), explore=True)
-    assert b2.shape == (1, 200) and s2.shape == (1, 30) and a2.shape == (1, A)
+    assert b2.shape == (1, D) and s2.shape == (1, S) and a2.shape == (1, A)
     assert float(a2.abs().max()) <= 1.0
     np.testing.assert_allclose(b2.cpu().numpy(), ob.numpy(), rtol=1e-4, atol=1e-5)
 

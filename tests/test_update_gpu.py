@@ -65,7 +65,7 @@ def make_agent(algo, L, B, H, A, seed=7, image=64, **over):
     set_gpu_mode(True)
     cfg = fx.default_config(algo=algo, batch_size=B, chunk_size=L, horizon=H, **over)
     agent = (RePo if algo == "repo" else Dreamer)(cfg, Env(A, image), Env(A, image), Logger())
-    params = fx.make_params(A, seed, image, belief=cfg.belief_size, state=cfg.state_size)
+    params = fx.make_params(A, seed, image, belief=cfg.belief_size, state=cfg.state_size, hidden=cfg.hidden_size)
     for mod in fx.MODULES:
         sd = {k: torch.from_numpy(v) for k, v in params[mod].items()}
         agent._load_module(getattr(agent, mod), sd)
@@ -299,6 +299,88 @@ def test_train_dynamics_at_other_latent_widths_matches_oracle(algo, belief, stat
     assert e < 1e-3, e
     for shape, x in errs:
         assert x < 5e-3, (shape, x)
+
+
+# The whole update -- train_dynamics AND train_actor_critic (rollout, actor, value) -- at the widths of
+# tests/test_widths_gpu.py that take other engines than the default: (belief, hidden, state, action).
+WIDTH_UPDATES = [
+    pytest.param(208, 208, 32, 16, id="full-blocks"),
+    pytest.param(200, 208, 30, 6, id="hidden-ne-belief"),
+    pytest.param(200, 200, 31, 6, id="odd-state"),
+    pytest.param(200, 200, 30, 1, id="cartpole"),
+    pytest.param(200, 200, 30, 21, id="humanoid"),
+    pytest.param(256, 256, 32, 6, id="max-width"),
+]
+
+
+@pytest.mark.parametrize("belief,hidden,state,A", WIDTH_UPDATES)
+def test_update_at_other_widths_matches_oracle(belief, hidden, state, A):
+    L, B, H = 10, 5, 6
+    over = dict(belief_size=belief, hidden_size=hidden, state_size=state)
+    agent, cfg = make_agent("repo", L, B, H, A, **over)
+    oracle = OracleAgent(cfg, A, params=fx.make_params(A, 7, belief=belief, state=state, hidden=hidden))
+    tag = f"[oracle widths belief={belief} hidden={hidden} state={state} A={A}]"
+    for u in range(2):
+        batch, host = dev_batch(L, B, A, 60 + u, u8=(u == 0))
+        agent.noise_source, nz = dev_noise(L, B, H, A, 160 + u, state=state)
+        with grad_snapshots(agent) as snap:
+            beliefs, post = agent.train_dynamics(batch[0], batch[1], batch[2], 1.0 - batch[3])
+            agent.train_actor_critic(beliefs.flatten(0, 1), post.flatten(0, 1))
+        ob, op_, oscal = oracle.update(*host, nz)
+        assert beliefs.shape == (L - 1, B, belief) and post.shape == (L - 1, B, state)
+        tol = 1e-4 if u == 0 else 2e-3
+        np.testing.assert_allclose(beliefs.cpu().numpy(), ob.numpy(), rtol=1e-3, atol=tol)
+        np.testing.assert_allclose(post.cpu().numpy(), op_.numpy(), rtol=1e-3, atol=tol)
+        for k, w in oscal.items():
+            got = agent.last_scalars[k]
+            assert abs(got - w) <= 1e-3 * abs(w) + 1e-7, (u, k, got, w)
+        for name, grads in (("model", oracle.last["model_grads"]), ("actor", oracle.last["actor_grads"]),
+                            ("value", oracle.last["value_grads"])):
+            opt = getattr(agent, f"{name}_optimizer")
+            want = torch.zeros(opt.numel)
+            for gr, o, q in zip(grads, opt.offsets, opt.params):
+                if gr is not None:
+                    want[o : o + q.numel()] = gr.reshape(-1)
+            e = ((snap[name].cpu() - want).norm() / want.norm()).item()
+            errs = per_tensor_errors(snap[name], grads, opt)
+            log(f"{tag} update {u} {name}: flat {e:.2e}; per-tensor worst {max(x for _, x in errs):.2e} "
+                + " ".join(f"{x:.1e}" for _, x in errs))
+            assert e < 1e-3, (name, e)
+            for shape, x in errs:
+                assert x < 5e-3, (name, shape, x)
+        # as in test_update_matches_oracle_latents_and_grads at 512 rows: the oracle takes the agent's parameters, so the
+        # second update's gradients are compared at the same point (encoder ReLU ties within rounding of zero, turned into
+        # parameter differences by Adam's sign-like first step, moved conv1's second gradient by up to 1.2e-2)
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            for m in fx.MODULES:
+                for k, v in getattr(agent, m).state_dict().items():
+                    oracle.p[m][k].copy_(v.cpu())
+            oracle.log_beta.copy_(agent.log_beta.cpu().reshape(oracle.log_beta.shape))
+
+
+@pytest.mark.parametrize("belief,state,A,entry", [(264, 30, 6, "repo_rssm_observe_fwd"),
+                                                  (200, 30, 40, "repo_rssm_observe_fwd")])
+def test_update_at_unsupported_widths_raises_and_leaves_the_model(belief, state, A, entry):
+    """belief_size above the row scan's 256 features, and state + action above its 64 columns: the first update raises
+    RepoHipError naming the entry point that refused the shape -- no NaN or stale numbers, and no optimiser has stepped."""
+    from repo_amd._lib import RepoHipError
+
+    L, B, H = 6, 3, 4
+    agent, cfg = make_agent("repo", L, B, H, A, belief_size=belief, state_size=state)
+    batch, _ = dev_batch(L, B, A, 70)
+    agent.noise_source, _ = dev_noise(L, B, H, A, 170, state=state)
+    opts = (agent.model_optimizer, agent.actor_optimizer, agent.value_optimizer)
+    before = [t.clone() for o in opts for t in (o.flat, o.exp_avg, o.exp_avg_sq)] + [agent.log_beta.clone()]
+    steps = [o.step_count for o in opts]
+    with pytest.raises(RepoHipError, match=entry):
+        agent.update(batch)
+        agent.last_scalars
+    torch.cuda.synchronize()
+    after = [t for o in opts for t in (o.flat, o.exp_avg, o.exp_avg_sq)] + [agent.log_beta]
+    assert [o.step_count for o in opts] == steps
+    for i, (a, b) in enumerate(zip(before, after)):
+        assert torch.equal(a, b), i
 
 
 def test_full_size_update_properties():
