@@ -1,20 +1,14 @@
-// Stride-2 convolution family of the reference's encoder/decoder on the igemm tile engine.
+// Stride-2 convolution family of the reference's encoder/decoder: three passes (down, up, weight gradient) of 14 layer
+// geometries over eleven engine headers.  Which engine a layer's pass takes is written down once, in the table under
+// "host-side dispatch" (Layer<G>), and decided per call by down_plan / up_plan / wgrad_plan there.
 //
-// A layer is a (big, small) pair with big = 2*small + KS - 2 and one weight tensor
-// w[cs][cb][ky][kx] (nn.Conv2d (out,in,kh,kw) for the encoder, nn.ConvTranspose2d
-// (in,out,kh,kw) for the decoder -- the same indexing).  GEMM roles put channels on M and
-// pixels on N so the epilogue's lanes run along the contiguous pixel index of NCHW.
-//
+// A layer is a (big, small) pair with big = 2*small + KS - 2 and one weight tensor w[cs][cb][ky][kx] (nn.Conv2d
+// (out,in,kh,kw) for the encoder, nn.ConvTranspose2d (in,out,kh,kw) for the decoder -- the same indexing).
 //   down : small[img][cs][sy][sx] = sum_{cb,ky,kx} big[img][cb][2sy+ky][2sx+kx] w[cs][cb][ky][kx]
-//          M = CS, N = nimg*HS*WS, K = CB*KS*KS                 (A = weights, k-contiguous)
-//   up   : for each output parity class (py,px):
-//          big[img][cb][2y+py][2x+px] = sum_{cs,jy,jx} small[img][cs][y-jy][x-jx] w[cs][cb][py+2jy][px+2jx]
-//          M = CB, N = nimg*ny*nx, K = CS*JY*JX  -- only the taps that exist, no zero-stuffing
-//   upm  : the four classes merged on M (M = 4*CB) for CB = 3, where a 32-row tile per class
-//          would waste 29 rows; the taps (3x3 for k=6) are shared by all four classes.
+//   up   : big[img][cb][2y+py][2x+px] = sum_{cs,jy,jx} small[img][cs][y-jy][x-jx] w[cs][cb][py+2jy][px+2jx] per output
+//          parity class (py,px): only the taps that exist, no zero-stuffing
 //   wgrad: dw[cs][cb][ky][kx] = sum_{img,sy,sx} small[img][cs][sy][sx] big[img][cb][2sy+ky][2sx+kx]
-//          M = CS, N = CB*KS*KS (+1 column of ones = bias gradient of `small`), K = nimg*HS*WS
-//          split over images into slabs, reduced in fixed order.
+//          (+ the bias gradient of `small`), split over images into slabs, reduced in fixed order
 #include <stdlib.h>
 
 #include <algorithm>
@@ -31,7 +25,6 @@
 #include "twgrad.h"
 #include "tconv_up.h"
 #include "tconv_down.h"
-
 
 namespace repo {
 
@@ -388,89 +381,208 @@ __global__ void relu_mask_kernel(int64_t n, const float* __restrict__ dy, const 
 }
 
 // ------------------------------------------------------------------------------- host-side dispatch
-// direct-conv tiles per layer: <BM, BN, CK, WM, WN>
-template <class G>
-struct DTileFor;
-// wgrad tiles: <BM, BN, WM, WN, images per chunk, small rows per chunk>; WGT = workgroups the split-K over image
-// groups aims at (sweep of 768 / 1024 / 1536 / 2048 / 3072 on one box, round 3: enc2 371 -> 335 us at 768, enc3
-// 239 -> 226 at 1024, dec3 542 -> 531 at 2048; fewer splits also mean smaller slabs to reduce)
-// the 3-channel layers are one channel chunk per workgroup (no pipelining inside it): 8 waves per tile and short
+// What is chosen per LAYER is one table entry, Layer<G> below.  What is chosen per CALL is one plan per pass (down_plan,
+// up_plan, wgrad_plan): a plain struct computed from the run-time arguments, which the workspace-size query, the pack and
+// the launcher all consume.  Moving a layer's pass to another engine = editing its entry; nothing else derives a tile
+// count, a pack size or a workspace offset.
+struct Off {};   // "not on this engine"
+template <class T> constexpr bool kOn = !std::is_same<T, Off>::value;
+
+// Every layer has the fp32-MFMA kernels of dconv.h: the down pass's throughput tile DTile <BM, BN, CK, WM, WN>, the weight
+// gradient's WTile <BM, BN, WM, WN, images per chunk, small rows per chunk> and WGT, the workgroups its split-K over image
+// groups aims at.  The other engines are off unless the entry names them.
+template <class Down_, class Wgrad_, int WGT_>
+struct LayerFp32 {
+  using Down = Down_; using Wgrad = Wgrad_; static constexpr int WGT = WGT_;
+  // -- down.  A handful of frames (the acting path encodes ONE per environment step): the throughput tiles leave 1-2
+  // workgroups walking 16-64 dependent channel chunks (enc4: 147 us for one frame).  Latency tiles (nimg * PS <= 512) use 32
+  // output channels per workgroup (4-8x more workgroups) and 4x larger channel chunks (4x fewer barriers).  Off = `Down`.
+  using DownLat = Off;
+  // bconv.h (bf16x6) for the MFMA-bound geometries with an even big-row pitch; the 3-channel layers are bandwidth bound ...
+  using DownBf = Off;
+  // ... but for uint8 frames (the encoder's first layer as train_agent() feeds it): the bytes are exact in ONE bf16, so the
+  // product needs three MFMAs per block instead of six and no split of the activation (bconv.h, U8)
+  using DownBfU8 = Off;
+  // tconv_down.h (staging waves beside multiplying waves): its geometry.  It takes a call of the bf16x6 kernel's, and its
+  // pack that kernel's place, if nimg >= 32, no channel sums are wanted and down_tcd_takes(epi, has_bias, wants_cmask).
+  using DownTcd = Off;
+  static bool down_tcd_takes(int, bool, bool) { return false; }
+  // -- up: with none of these, the merged gather engine (igemm.h, ConvUpMergedOp)
+  using UpScatter = Off;   // uconv.h: SConf <images per workgroup, resident N tiles>
+  // buconv.h, the scatter kernel in bf16x6 (the decoder's conv3 forward is the update's largest launch).  The weight pack's
+  // format follows the kernel: repo_debug_bconv toggles both, a pack written under one setting is void under the other.
+  using UpBfScatter = Off;
+  // dconv_up.h (direct, register-accumulating): its tile, instead of a scatter configuration.  A/B on one box (round 3, us):
+  //   enc2@128 data gradient  gather engine 1634 -> direct 1243 (8 waves; 4 waves 1424)
+  //   dec4@128 forward        gather engine  717 -> direct  535
+  //   TIA conv4 forward       gather engine  775 -> direct  434
+  //   enc2 data gradient      scatter        425 vs direct  606 (its K loop alone runs 424, staging +76, epilogue
+  //                           +106; staggered starts, 16-byte-aligned stores and prefetching the ReLU operand under
+  //                           the last chunk's MFMAs each changed nothing): the scatter kernel stays
+  using DirectUp = Off;
+  // tconv_up.h (gather form): takes the encoder backward's epilogues at nimg >= 4; its pack sits behind the scatter kernels'
+  static constexpr bool UpTconv = false;
+  // -- weight gradient
+  // bwgrad.h (bf16x6, on the fp32 kernel's split-K) for the layers whose bands fill whole 16-k blocks reasonably (enc4's
+  // 2 x 2 planes would run 4 real k in a block of 16; the 3-channel layers are not MFMA-bound).  Measured and left on the fp32
+  // kernel: enc2 (31 x 31 planes: 343-445 us against 320) and dec2 (232-244 against 247) -- with one or two waves per SIMD the
+  // in-register split of the B fragments (44 dependent vector instructions per 8 elements) is not hidden behind 12 MFMAs
+  using WgradBf = Off;
+  // twgrad.h (both operands split at staging, `big` read through the LDS's transposing load): k-blocks per chunk, 0 = not
+  // on this engine; staging waves: 8 where the multiplying waves (4 taps: 64 accumulator registers) fit three waves per
+  // SIMD.  A PAIR of workgroups (the two row parities of the taps) owns the whole dw of its images: images per split =
+  // ceil(nimg / 128), one slab per pair.  TwDbig: the channel sums of `big` ride along where the taps cover it.
+  static constexpr int TwNBK = 0, TwNPW = 4;
+  static constexpr bool TwDbig = true;
+};
+
+template <class G> struct Layer;
+// WGT: sweep of 768 / 1024 / 1536 / 2048 / 3072 on one box, round 3: enc2 371 -> 335 us at 768, enc3 239 -> 226 at 1024,
+// dec3 542 -> 531 at 2048; fewer splits also mean smaller slabs to reduce.
+// The 3-channel layers are one channel chunk per workgroup (no pipelining inside it): 8 waves per tile and short
 // weight-gradient bands measured best (tile sweep, round 2: enc1 fwd 148 -> 140 us, enc1 wgrad 224 -> 171,
 // dec4 dgrad 311-338 -> 247, dec4 wgrad 210 -> 201)
-template <> struct DTileFor<GEnc1> { using Down = DTile<32, 512, 3, 1, 8>; using Wgrad = WTile<32, 64, 1, 2, 1, 4, 2>; static constexpr int WGT = 3072; };
-template <> struct DTileFor<GEnc2> { using Down = DTile<64, 128, 2, 2, 2>; using Wgrad = WTile<64, 128, 2, 2, 1, 7, 2>; static constexpr int WGT = 768; };
-template <> struct DTileFor<GEnc3> { using Down = DTile<128, 128, 2, 2, 2>; using Wgrad = WTile<64, 128, 2, 2, 2, 6>; static constexpr int WGT = 1024; };
+template <> struct Layer<GEnc1> : LayerFp32<DTile<32, 512, 3, 1, 8>, WTile<32, 64, 1, 2, 1, 4, 2>, 3072> {
+  using DownBfU8 = BTile<32, 512, 4, 1, 8>;
+};
+template <> struct Layer<GEnc2> : LayerFp32<DTile<64, 128, 2, 2, 2>, WTile<64, 128, 2, 2, 1, 7, 2>, 768> {
+  using DownLat = DTile<32, 128, 4, 1, 4>;
+  // 31 x 31 planes, k4: with the element-wise staging of its padded pitch it measured equal on both kernels (312 vs 309 us,
+  // round 4); staged by LDS quads (bconv.h, QROW) it is on the bf16 pipe
+  using DownBf = BTile<64, 256, 4, 1, 4>;
+  // its forward (ReLU) runs on tconv_down.h since round 6 (242 -> 203 us alone, results within 3e-6 of fp64, masks identical
+  // to the fp32 engine's on random data).  Round 5 built it and left it un-routed: on the TIA oracle test's frames its 5e-7
+  // differences flip ONE ReLU decision of conv3 at a pre-activation 5e-7 from zero, and that pixel alone takes the encoder's
+  // gradient 5e-3 from the oracle's -- the test now hands the oracle the kernels' decision inside a 1e-5 band around zero
+  // (tests/test_tia_gpu.py, _TIE_BAND).
+  using DownTcd = TcdGeoE2;
+  static bool down_tcd_takes(int epi, bool, bool) { return epi == REPO_EPI_RELU; }
+  using UpScatter = SConf<GEnc2, 1, 8>;
+  using UpBfScatter = BSConf<GEnc2, 1, 4>;
+  static constexpr bool UpTconv = true;
+  static constexpr int TwNBK = 2, TwNPW = 8;
+};
+template <> struct Layer<GEnc3> : LayerFp32<DTile<128, 128, 2, 2, 2>, WTile<64, 128, 2, 2, 2, 6>, 1024> {
+  using DownLat = DTile<32, 128, 8, 1, 4>;
+  // enc3 / enc4: ONE M tile per workgroup (the patch is staged and split once): 169 -> 146 us, 112 -> 101 (round 5)
+  using DownBf = BTile<128, 128, 4, 2, 2>;
+  using UpScatter = SConf<GEnc3, 4, 2>;
+  using UpBfScatter = BSConf<GEnc3, 4, 4>;      // CS = 128: two K-slices
+  using WgradBf = WTile<64, 256, 1, 4, 1, 6>;   // 215 -> 172-182 us
+};
 // enc4 forward has only 9800 output pixels: 128 x 128 tiles are 154 workgroups on 256 CUs (171 us); 32 x 64: 125 us
-template <> struct DTileFor<GEnc4> { using Down = DTile<32, 64, 2, 1, 2>; using Wgrad = WTile<64, 128, 2, 2, 8, 2>; static constexpr int WGT = 768; };
+template <> struct Layer<GEnc4> : LayerFp32<DTile<32, 64, 2, 1, 2>, WTile<64, 128, 2, 2, 8, 2>, 768> {
+  using DownLat = DTile<32, 128, 8, 1, 4>;
+  using DownBf = BTile<128, 64, 4, 2, 2>;
+  using UpScatter = SConf<GEnc4, 8, 1>;
+  using UpBfScatter = BSConf<GEnc4, 8, 2>;   // CS = 256: four
+};
 // (dec2 down: 8 waves, 306 -> 274 us, A/B on one box)
-template <> struct DTileFor<GDec2> { using Down = DTile<128, 128, 4, 2, 4, 1>; using Wgrad = WTile<64, 128, 2, 2, 4, 5>; static constexpr int WGT = 1536; };
-template <> struct DTileFor<GDec3> { using Down = DTile<64, 128, 2, 2, 2>; using Wgrad = WTile<64, 128, 2, 2, 1, 7>; static constexpr int WGT = 2048; };
-template <> struct DTileFor<GDec4> { using Down = DTile<32, 256, 3, 1, 8>; using Wgrad = WTile<32, 128, 1, 4, 1, 2>; static constexpr int WGT = 1536; };
-// 128 x 128 stack: tiles by analogy with the 64 x 64 layer of the same role (not swept)
+template <> struct Layer<GDec2> : LayerFp32<DTile<128, 128, 4, 2, 4, 1>, WTile<64, 128, 2, 2, 4, 5>, 1536> {
+  using DownBf = BTile<64, 128, 2, 1, 4>;    // 13 x 13 planes, k5 (32 slots for 25 taps)
+  using UpScatter = SConf<GDec2, 5, 2>;
+  using UpBfScatter = BSConf<GDec2, 5, 4>;   // CS = 128, k5: per-class tap sets
+};
+template <> struct Layer<GDec3> : LayerFp32<DTile<64, 128, 2, 2, 2>, WTile<64, 128, 2, 2, 1, 7>, 2048> {
+  using DownBf = BTile<64, 256, 2, 1, 4>;
+  using DownTcd = TcdGeo;   // its data gradient: plain or times the ReLU derivative, nothing else
+  static bool down_tcd_takes(int epi, bool has_bias, bool wants_cmask) {
+    return (epi == REPO_EPI_NONE || epi == REPO_EPI_MUL_DRELU) && !has_bias && !wants_cmask;
+  }
+  using UpScatter = SConf<GDec3, 1, 6>;
+  using UpBfScatter = BSConf<GDec3, 1, 4>;
+  using WgradBf = WTile<64, 128, 1, 4, 1, 7>;   // 531 -> 465 us (64 x 64 wave tiles: 551)
+  static constexpr int TwNBK = 2;
+};
+template <> struct Layer<GDec4> : LayerFp32<DTile<32, 256, 3, 1, 8>, WTile<32, 128, 1, 4, 1, 2>, 1536> {};
+// 128 x 128 stack: tiles by analogy with the 64 x 64 layer of the same role (not swept).  Up: the parity-class planes of a
+// 16-channel group must fit LDS (<= 80 KB: two workgroups per CU), which 30 x 30 and 14 x 14 outputs do; 63 x 63 / 64 x 64
+// / 128 x 128 outputs (262 KB) take the direct kernel or the gather engine.
 // (GX1's weight gradient walks 2-row bands: with 4 rows of 63 pixels the 126 k-pairs of a band exceed what the
 // compiler unrolls, the chunk-ahead loads then index their registers at run time: 1935 us instead of ~400)
-template <> struct DTileFor<GX1> { using Down = DTile<32, 512, 3, 1, 8>;  using Wgrad = WTile<32, 64, 1, 2, 1, 2, 2>; static constexpr int WGT = 3072; };
-template <> struct DTileFor<GX2> { using Down = DTile<64, 128, 2, 2, 2>;  using Wgrad = WTile<64, 128, 2, 2, 1, 3, 2>; static constexpr int WGT = 1536; };
-template <> struct DTileFor<GX3> { using Down = DTile<128, 128, 2, 2, 2>; using Wgrad = WTile<64, 128, 2, 2, 1, 7>; static constexpr int WGT = 1024; };
-template <> struct DTileFor<GX4> { using Down = DTile<64, 128, 2, 2, 2>;  using Wgrad = WTile<64, 128, 2, 2, 2, 6>; static constexpr int WGT = 1024; };
-template <> struct DTileFor<GY4> { using Down = DTile<32, 256, 2, 1, 4>;  using Wgrad = WTile<32, 128, 1, 4, 1, 2>; static constexpr int WGT = 1536; };
-template <> struct DTileFor<GT4> { using Down = DTile<32, 256, 3, 1, 8>;  using Wgrad = WTile<32, 128, 1, 4, 1, 2>; static constexpr int WGT = 1536; };
-template <> struct DTileFor<GY5> { using Down = DTile<32, 512, 3, 1, 8>;  using Wgrad = WTile<32, 64, 1, 2, 1, 2>; static constexpr int WGT = 1536; };
+template <> struct Layer<GX1> : LayerFp32<DTile<32, 512, 3, 1, 8>, WTile<32, 64, 1, 2, 1, 2, 2>, 3072> {};
+template <> struct Layer<GX2> : LayerFp32<DTile<64, 128, 2, 2, 2>, WTile<64, 128, 2, 2, 1, 3, 2>, 1536> {
+  using DirectUp = DTile<128, 128, 8, 2, 4>;
+};
+template <> struct Layer<GX3> : LayerFp32<DTile<128, 128, 2, 2, 2>, WTile<64, 128, 2, 2, 1, 7>, 1024> {
+  using UpScatter = SConf<GX3, 1, 2>;
+};
+template <> struct Layer<GX4> : LayerFp32<DTile<64, 128, 2, 2, 2>, WTile<64, 128, 2, 2, 2, 6>, 1024> {
+  using UpScatter = SConf<GX4, 4, 1>;
+};
+template <> struct Layer<GY4> : LayerFp32<DTile<32, 256, 2, 1, 4>, WTile<32, 128, 1, 4, 1, 2>, 1536> {
+  using DirectUp = DTile<64, 256, 4, 2, 4>;
+};
+template <> struct Layer<GY5> : LayerFp32<DTile<32, 512, 3, 1, 8>, WTile<32, 64, 1, 2, 1, 2>, 1536> {};
+template <> struct Layer<GT4> : LayerFp32<DTile<32, 256, 3, 1, 8>, WTile<32, 128, 1, 4, 1, 2>, 1536> {
+  using DirectUp = DTile<32, 256, 4, 1, 8>;
+};
 
-// A handful of frames (the acting path encodes ONE per environment step): the throughput tiles leave 1-2
-// workgroups walking 16-64 dependent channel chunks (enc4: 147 us for one frame).  Latency tiles use 32
-// output channels per workgroup (4-8x more workgroups) and 4x larger channel chunks (4x fewer barriers).
-template <class G> struct DLatTile { using type = typename DTileFor<G>::Down; };
-template <> struct DLatTile<GEnc2> { using type = DTile<32, 128, 4, 1, 4>; };
-template <> struct DLatTile<GEnc3> { using type = DTile<32, 128, 8, 1, 4>; };
-template <> struct DLatTile<GEnc4> { using type = DTile<32, 128, 8, 1, 4>; };
+// What the plans read: the table entry under the A/B builds' overrides (tools/build_variant.sh).  -DTCD_DISABLE: bconv.h
+// instead of tconv_down.h, -DTCD_NO_ENC2: for encoder conv2 only; -DTCU_DISABLE: the scatter kernel instead of tconv_up.h;
+// -DTW_DISABLE: the previous weight-gradient engines instead of twgrad.h; -DTW_NO_DBIG: the separate channel-sum pass.
+template <class G> struct Route : Layer<G> {
+#if defined(TCD_DISABLE)
+  using DownTcd = Off;
+#elif defined(TCD_NO_ENC2)
+  using DownTcd = std::conditional_t<std::is_same<G, GEnc2>::value, Off, typename Layer<G>::DownTcd>;
+#endif
+#ifdef TCU_DISABLE
+  static constexpr bool UpTconv = false;
+#endif
+#ifdef TW_DISABLE
+  static constexpr int TwNBK = 0;
+#endif
+#ifdef TW_NO_DBIG
+  static constexpr bool TwDbig = false;
+#endif
+};
+template <class G> using DownLatTile = std::conditional_t<kOn<typename Route<G>::DownLat>, typename Route<G>::DownLat, typename Route<G>::Down>;
+template <class G, class BigT> using DownBfTile = std::conditional_t<std::is_same<BigT, float>::value, typename Route<G>::DownBf, typename Route<G>::DownBfU8>;
 
-// The bf16x6 down kernel (bconv.h: fp32-accurate, six bf16 MFMAs per 16 k) for the MFMA-bound geometries with an even
-// big-row pitch; NoBTile = the layer stays on the fp32-MFMA kernel (3-channel layers: bandwidth / epilogue bound).  Test aid repo_debug_bconv(0) keeps every layer on the fp32 kernel.
-struct NoBTile {};
-template <class G> struct BDownFor { using type = NoBTile; };
-template <> struct BDownFor<GDec3> { using type = BTile<64, 256, 2, 1, 4>; };
-// enc3 / enc4: ONE M tile per workgroup (the patch is staged and split once): 169 -> 146 us, 112 -> 101 (round 5)
-template <> struct BDownFor<GEnc3> { using type = BTile<128, 128, 4, 2, 2>; };
-template <> struct BDownFor<GEnc4> { using type = BTile<128, 64, 4, 2, 2>; };
-// enc2 forward (31 x 31 planes, k4): with the element-wise staging of its padded pitch it measured equal on both kernels
-// (312 vs 309 us, round 4); staged by LDS quads (bconv.h, QROW) it is on the bf16 pipe
-template <> struct BDownFor<GEnc2> { using type = BTile<64, 256, 4, 1, 4>; };
-template <> struct BDownFor<GDec2> { using type = BTile<64, 128, 2, 1, 4>; };   // 13 x 13 planes, k5 (32 slots for 25 taps)
-template <class G> constexpr bool kBDown = !std::is_same<typename BDownFor<G>::type, NoBTile>::value;
-// ... and for uint8 frames (the encoder's first layer as train_agent() feeds it): the bytes are exact in ONE bf16, so the
-// product needs three MFMAs per block instead of six and no split of the activation (bconv.h, U8); float frames of the
-// same layer stay on the fp32 kernel.
-template <class G> struct BDownU8For { using type = NoBTile; };
-template <> struct BDownU8For<GEnc1> { using type = BTile<32, 512, 4, 1, 8>; };
-template <class G> constexpr bool kBDownU8 = !std::is_same<typename BDownU8For<G>::type, NoBTile>::value;
+constexpr size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// ---- down.  Workspace: [weight pack of the bf16x6 kernel | channel-sum partials]; without room for the pack the layer
+// runs on the fp32-MFMA kernel (ws stays optional for callers that want no dbias).  Test aid repo_debug_bconv(0) keeps
+// every layer on the fp32 kernel.
+enum class DownEngine { Fp32Lat, Fp32, Bf16, Tcd };
+struct DownPlan {
+  DownEngine engine;
+  long tiles;          // pixel tiles of the engine's grid = rows of the channel-sum partials (repo_conv_down's dbias)
+  size_t pack_bytes;   // the weight pack at the head of the workspace = offset of the partials
+  size_t parts_bytes;  // 0 unless the channel sums are wanted
+  size_t need() const { return pack_bytes + parts_bytes; }
+};
 template <class G, class BigT>
-constexpr bool kBDownT = std::is_same<BigT, float>::value ? kBDown<G> : kBDownU8<G>;
-template <class G, class BigT>
-using BDownTile = typename std::conditional<std::is_same<BigT, float>::value, typename BDownFor<G>::type, typename BDownU8For<G>::type>::type;
-
-template <class G, class BigT = float>
-static bool bconv_down_on(int64_t nimg) {
-  if constexpr (kBDownT<G, BigT>) return t_bconv_enabled && nimg * (int64_t)G::PS > 512;
-  return false;
-}
-template <class G, class BigT = float>
-static size_t bconv_pack_bytes() {
-  if constexpr (kBDownT<G, BigT>) {
-    typedef BPack<G, BDownTile<G, BigT>> P;
-    return ((std::is_same<BigT, float>::value ? P::BYTES : P::BYTES_U8) + 255) & ~(size_t)255;
-  }
-  return 0;
-}
-
-// pixel tiles of the direct conv's grid = rows of the channel-sum partials (repo_conv_down's dbias)
-template <class G, class BigT = float>
-static long conv_down_tiles(int64_t nimg) {
+static DownPlan down_plan(int64_t nimg, int epi, bool has_bias, bool wants_dbias, bool wants_cmask, size_t ws_have) {
+  using R = Route<G>;
+  using BT = DownBfTile<G, BigT>;
   const long px = nimg * (long)G::PS;
-  long bn = px <= 512 ? DLatTile<G>::type::BN : DTileFor<G>::Down::BN;
-  if constexpr (kBDownT<G, BigT>)
-    if (bconv_down_on<G, BigT>(nimg)) bn = BDownTile<G, BigT>::BN;
-  return (px + bn - 1) / bn;
+  auto plan = [&](DownEngine e, long bn, size_t pack) {
+    const long tiles = (px + bn - 1) / bn;
+    return DownPlan{e, tiles, pack, wants_dbias ? (size_t)tiles * G::CS * sizeof(float) : 0};
+  };
+  if constexpr (kOn<BT>) {
+    if (t_bconv_enabled && px > 512) {
+      using P = BPack<G, BT>;
+      constexpr size_t pack = round256(std::is_same<BigT, float>::value ? P::BYTES : P::BYTES_U8);
+      DownPlan b = plan(DownEngine::Bf16, BT::BN, pack);
+      if constexpr (kOn<typename R::DownTcd>) {
+        static_assert(std::is_same<BigT, float>::value && R::DownTcd::PACK_BYTES <= pack,
+                      "tconv_down: float frames; its pack fits the room of the bf16x6 kernel's");
+        if (nimg >= 32 && !wants_dbias && R::down_tcd_takes(epi, has_bias, wants_cmask)) b.engine = DownEngine::Tcd;
+      }
+      if (ws_have >= b.need()) return b;
+    }
+  }
+  return px <= 512 ? plan(DownEngine::Fp32Lat, DownLatTile<G>::BN, 0) : plan(DownEngine::Fp32, R::Down::BN, 0);
+}
+// (the frame type is not known to the size query: the larger pack and the larger partials of the float / uint8 plans)
+template <class G>
+static size_t conv_down_ws_bytes(int64_t nimg) {
+  const DownPlan f = down_plan<G, float>(nimg, REPO_EPI_NONE, false, true, false, SIZE_MAX);
+  const DownPlan u = down_plan<G, uint8_t>(nimg, REPO_EPI_NONE, false, true, false, SIZE_MAX);
+  return std::max(f.pack_bytes, u.pack_bytes) + std::max(f.parts_bytes, u.parts_bytes);
 }
 
 template <class G, class BigT>
@@ -479,179 +591,117 @@ static int conv_down_t(int64_t nimg, const BigT* big, const float* w, const floa
                        size_t ws_bytes, hipStream_t s) {
   if (cmask && G::CS % 4 != 0) return REPO_E_BADARG;
   if (nimg * (int64_t)G::CB * G::PB >= kMaxBufElems || nimg * (int64_t)G::CS * G::PS >= kMaxBufElems) return REPO_E_SHAPE;
-  // workspace: [weight pack of the bf16x6 kernel | channel-sum partials]; without room for the pack the layer runs
-  // on the fp32-MFMA kernel (ws stays optional for callers that want no dbias)
-  bool bf = false;
-  size_t pack_bytes = 0;
-  if constexpr (kBDownT<G, BigT>) {
-    pack_bytes = bconv_pack_bytes<G, BigT>();
-    bf = bconv_down_on<G, BigT>(nimg) && ws && ws_bytes >= pack_bytes + (dbias ? (size_t)conv_down_tiles<G, BigT>(nimg) * G::CS * sizeof(float) : 0);
-    if (!bf) pack_bytes = 0;
-  }
-  long tiles = conv_down_tiles<G, BigT>(nimg);
-  if constexpr (kBDownT<G, BigT>)
-    if (!bf && bconv_down_on<G, BigT>(nimg)) {   // the pack did not fit: the fp32 kernel's grid
-      const long px = nimg * (long)G::PS;
-      tiles = (px + DTileFor<G>::Down::BN - 1) / DTileFor<G>::Down::BN;
-    }
-  if (dbias && (!ws || ws_bytes < pack_bytes + (size_t)tiles * G::CS * sizeof(float))) return REPO_E_WS_TOO_SMALL;
-  float* parts = dbias ? (float*)((char*)ws + pack_bytes) : nullptr;
+  const size_t ws_have = ws ? ws_bytes : 0;
+  const DownPlan p = down_plan<G, BigT>(nimg, epi, bias != nullptr, dbias != nullptr, cmask != nullptr, ws_have);
+  if (ws_have < p.need()) return REPO_E_WS_TOO_SMALL;
+  float* parts = dbias ? (float*)((char*)ws + p.pack_bytes) : nullptr;
   DownArgs a{big, w, bias, aux, small, (int)nimg, epi, (unsigned)(nimg * G::CB * G::PB * sizeof(BigT)),
              (unsigned)(G::CS * G::CB * G::KK * sizeof(float)), parts, cmask};
-  int rc;
-#ifndef TCD_DISABLE
-  // staging waves beside multiplying waves (tconv_down.h): decoder conv3's data gradient; the kernel's pack takes the bf16x6
-  // kernel's place in the workspace.  Encoder conv2's forward runs on the same kernel since round 6 (242 -> 203 us alone,
-  // results within 3e-6 of fp64, masks identical to the fp32 engine's on random data; -DTCD_NO_ENC2 = bconv_down, for A/B).
-  // Round 5 built it and left it un-routed: on the TIA oracle test's frames its 5e-7 differences flip ONE ReLU decision of
-  // conv3 at a pre-activation 5e-7 from zero, and that pixel alone takes the encoder's gradient 5e-3 from the oracle's --
-  // the test now hands the oracle the kernels' decision inside a 2e-6 band around zero (tests/test_tia_gpu.py).
-  if constexpr (std::is_same<G, GDec3>::value && std::is_same<BigT, float>::value) {
-    if (bf && (epi == REPO_EPI_NONE || epi == REPO_EPI_MUL_DRELU) && !bias && !dbias && !cmask && nimg >= 32 &&
-        pack_bytes >= TcdGeo::PACK_BYTES)
-      return launch_tconv_down<TcdGeo>(a, w, (char*)ws, s);
-  }
-#ifndef TCD_NO_ENC2
-  if constexpr (std::is_same<G, GEnc2>::value && std::is_same<BigT, float>::value) {
-    if (bf && epi == REPO_EPI_RELU && !dbias && nimg >= 32 && pack_bytes >= TcdGeoE2::PACK_BYTES)
-      return launch_tconv_down<TcdGeoE2>(a, w, (char*)ws, s);
-  }
-#endif
-#endif
-  if constexpr (kBDownT<G, BigT>) {
-    if (bf) rc = launch_bconv_down<G, BDownTile<G, BigT>, BigT>(a, w, (char*)ws, s);
-    else rc = (nimg * (int64_t)G::PS <= 512) ? launch_dconv_down<G, BigT, typename DLatTile<G>::type>(a, s)
-                                            : launch_dconv_down<G, BigT, typename DTileFor<G>::Down>(a, s);
-  } else {
-    rc = (nimg * (int64_t)G::PS <= 512) ? launch_dconv_down<G, BigT, typename DLatTile<G>::type>(a, s)
-                                        : launch_dconv_down<G, BigT, typename DTileFor<G>::Down>(a, s);
+  int rc = REPO_E_BADARG;
+  switch (p.engine) {
+    case DownEngine::Tcd:
+      if constexpr (kOn<typename Route<G>::DownTcd>) rc = launch_tconv_down<typename Route<G>::DownTcd>(a, w, (char*)ws, s);
+      break;
+    case DownEngine::Bf16:
+      if constexpr (kOn<DownBfTile<G, BigT>>) rc = launch_bconv_down<G, DownBfTile<G, BigT>, BigT>(a, w, (char*)ws, s);
+      break;
+    case DownEngine::Fp32Lat: rc = launch_dconv_down<G, BigT, DownLatTile<G>>(a, s); break;
+    case DownEngine::Fp32: rc = launch_dconv_down<G, BigT, typename Route<G>::Down>(a, s); break;
   }
   if (rc || !dbias) return rc;
-  hipLaunchKernelGGL(channel_sum_final_kernel, dim3(cdiv(G::CS, 4)), dim3(256), 0, s, (const float*)parts, (int)tiles,
+  hipLaunchKernelGGL(channel_sum_final_kernel, dim3(cdiv(G::CS, 4)), dim3(256), 0, s, (const float*)parts, (int)p.tiles,
                      (int)G::CS, dbias, accumulate_dbias);
   REPO_CHECK_LAUNCH();
   return REPO_OK;
 }
 
-// Scatter-form configuration per geometry: images per workgroup, resident N tiles, weight prefetch.
-template <class G> struct UConf { using type = void; };
-template <> struct UConf<GDec3> { using type = SConf<GDec3, 1, 6>; };
-template <> struct UConf<GEnc2> { using type = SConf<GEnc2, 1, 8>; };
-template <> struct UConf<GDec2> { using type = SConf<GDec2, 5, 2>; };
-template <> struct UConf<GEnc3> { using type = SConf<GEnc3, 4, 2>; };
-template <> struct UConf<GEnc4> { using type = SConf<GEnc4, 8, 1>; };
-// 128 x 128 stack: the parity-class planes of a 16-channel group must fit LDS (<= 80 KB: two workgroups per CU), which
-// 30 x 30 and 14 x 14 outputs do; 63 x 63 / 64 x 64 / 128 x 128 outputs (262 KB) take the gather engine below
-template <> struct UConf<GX3> { using type = SConf<GX3, 1, 2>; };
-template <> struct UConf<GX4> { using type = SConf<GX4, 4, 1>; };
-
-// Direct (register-accumulating) transposed conv, dconv_up.h: tile per geometry, or NoTile = not used.  It takes
-// precedence over the scatter kernel / the gather engine where a tile is given.  A/B on one box (round 3, us):
-//   enc2@128 data gradient  gather engine 1634 -> direct 1243 (8 waves; 4 waves 1424)
-//   dec4@128 forward        gather engine  717 -> direct  535
-//   TIA conv4 forward       gather engine  775 -> direct  434
-//   enc2 data gradient      scatter        425 vs direct  606 (its K loop alone runs 424, staging +76, epilogue
-//                           +106; staggered starts, 16-byte-aligned stores and prefetching the ReLU operand under
-//                           the last chunk's MFMAs each changed nothing): the scatter kernel stays
-struct NoTile {};
-template <class G> struct UpDirect { using type = NoTile; };
-template <> struct UpDirect<GEnc2> { using type = NoTile; };
-template <> struct UpDirect<GEnc3> { using type = NoTile; };
-template <> struct UpDirect<GEnc4> { using type = NoTile; };
-template <> struct UpDirect<GDec2> { using type = NoTile; };
-template <> struct UpDirect<GDec3> { using type = NoTile; };
-template <> struct UpDirect<GX2> { using type = DTile<128, 128, 8, 2, 4>; };
-template <> struct UpDirect<GX3> { using type = NoTile; };
-template <> struct UpDirect<GX4> { using type = NoTile; };
-template <> struct UpDirect<GY4> { using type = DTile<64, 256, 4, 2, 4>; };
-template <> struct UpDirect<GT4> { using type = DTile<32, 256, 4, 1, 8>; };
-template <class G> constexpr bool kUpDirect = !std::is_same<typename UpDirect<G>::type, NoTile>::value;
-
-// The bf16x6 scatter kernel (buconv.h): the decoder's conv3 forward (the update's largest launch), conv2 forward, and the
-// encoder's conv2 / conv3 / conv4 data gradients.  The weight pack's format follows the kernel: repo_debug_bconv toggles both, so
-// a pack written under one setting must not be used under the other (tests re-pack).
-template <class G> struct BUConf { using type = void; };
-template <> struct BUConf<GDec3> { using type = BSConf<GDec3, 1, 4>; };
-template <> struct BUConf<GEnc2> { using type = BSConf<GEnc2, 1, 4>; };
-template <> struct BUConf<GEnc3> { using type = BSConf<GEnc3, 4, 4>; };   // CS = 128: two K-slices
-template <> struct BUConf<GEnc4> { using type = BSConf<GEnc4, 8, 2>; };   // CS = 256: four
-template <> struct BUConf<GDec2> { using type = BSConf<GDec2, 5, 4>; };   // CS = 128, k5: per-class tap sets
+// ---- up.  Workspace: [weight pack of the layer's scatter / direct kernel (room for either form of the scatter kernel: the
+// debug switch is thread-local) | pack of the gather-form kernel]; the merged gather engine reads the native weights.
+enum class UpEngine { Tconv, BfScatter, Direct, Scatter, Merged };
+struct UpPlan {
+  UpEngine engine;   // this call's
+  UpEngine base;     // the layer's where the gather-form kernel does not take the call: whose pack sits at offset 0
+  bool tcu_live;     // the gather-form kernel is in use (under the current debug switch): packing ahead writes its pack too
+  size_t tcu_off;    // ... at this offset
+  size_t need;       // bytes this call's engine reads
+  size_t total;      // bytes of the layer's packs together (repo_conv_up_workspace_bytes)
+};
 template <class G>
-static bool buconv_on() {
-  if constexpr (!std::is_void<typename BUConf<G>::type>::value) return t_bconv_enabled != 0;
-  return false;
-}
-
-template <class G>
-static size_t conv_up_ws_scatter() {
-  using C = typename UConf<G>::type;
-  using BC = typename BUConf<G>::type;
-  if constexpr (kUpDirect<G>) return UpGeo<G>::PACK_FLOATS * sizeof(float);
-  else if constexpr (std::is_void<C>::value) return 0;
-  else if constexpr (!std::is_void<BC>::value) return BC::PACK_BYTES > C::PACK_FLOATS * sizeof(float) ? BC::PACK_BYTES : C::PACK_FLOATS * sizeof(float);
-  else return C::PACK_FLOATS * sizeof(float);
-}
-// encoder conv2's data gradient also has a gather-form kernel (tconv_up.h): its pack sits behind the scatter kernels'
-template <class G> constexpr bool kTconvUp = false;
-#ifndef TCU_DISABLE   // A/B builds (tools/build_variant.sh)
-template <> constexpr bool kTconvUp<GEnc2> = true;
-#endif
-template <class G>
-static size_t conv_up_tcu_off() { return (conv_up_ws_scatter<G>() + 255) & ~(size_t)255; }
-template <class G>
-static size_t conv_up_ws_bytes() {
-  if constexpr (kTconvUp<G>) return conv_up_tcu_off<G>() + kTcuPackBytes;
-  return conv_up_ws_scatter<G>();
+static UpPlan up_plan(int64_t nimg, int epi, size_t ws_have) {
+  using R = Route<G>;
+  using UC = typename R::UpScatter;
+  using BC = typename R::UpBfScatter;
+  static_assert(!kOn<BC> || kOn<UC>, "the bf16x6 scatter kernel has an fp32 twin (repo_debug_bconv(0))");
+  static_assert(!kOn<typename R::DirectUp> || !kOn<UC>, "the direct kernel or the scatter kernels");
+  static_assert(!R::UpTconv || kOn<BC>, "the gather-form kernel follows the debug switch of the bf16x6 kernels");
+  UpPlan p{UpEngine::Merged, UpEngine::Merged, false, 0, 0, 0};
+  size_t room = 0;
+  if constexpr (kOn<BC>) {
+    p.base = t_bconv_enabled ? UpEngine::BfScatter : UpEngine::Scatter;
+    p.need = t_bconv_enabled ? BC::PACK_BYTES : UC::PACK_FLOATS * sizeof(float);
+    room = std::max(BC::PACK_BYTES, UC::PACK_FLOATS * sizeof(float));
+  } else if constexpr (kOn<typename R::DirectUp>) {
+    p.base = UpEngine::Direct, p.need = room = UpGeo<G>::PACK_FLOATS * sizeof(float);
+  } else if constexpr (kOn<UC>) {
+    p.base = UpEngine::Scatter, p.need = room = UC::PACK_FLOATS * sizeof(float);
+  }
+  p.engine = p.base;
+  p.tcu_off = round256(room);
+  p.total = R::UpTconv ? p.tcu_off + kTcuPackBytes : room;
+  p.tcu_live = R::UpTconv && t_bconv_enabled;
+  // the encoder backward's epilogues; ReLU / FiLM: the scatter kernel
+  const bool epi_ok = epi == REPO_EPI_NONE || epi == REPO_EPI_MUL_DRELU || epi == REPO_EPI_MUL_CMASK;
+  if (p.tcu_live && epi_ok && nimg >= 4 && ws_have >= p.total) {
+    p.engine = UpEngine::Tconv;
+    p.need = p.total;
+  }
+  return p;
 }
 
 template <class G>
 static int conv_up_pack_t(const float* w, void* ws, size_t ws_bytes, hipStream_t s) {
-  using UC = typename UConf<G>::type;
-  using BC = typename BUConf<G>::type;
-  if constexpr (kTconvUp<G>) {   // both packs: which kernel a later call takes depends on its epilogue and batch
-    if (buconv_on<G>()) {
-      if (!ws || ws_bytes < conv_up_ws_bytes<G>()) return REPO_E_WS_TOO_SMALL;
-      const int rc = launch_tconv_up_pack(w, (char*)ws + conv_up_tcu_off<G>(), s);
-      if (rc) return rc;
-    }
-  }
-  if constexpr (!std::is_void<BC>::value)
-    if (buconv_on<G>()) return launch_buconv_pack<G, BC>(w, ws, ws_bytes, s);
-  if constexpr (kUpDirect<G>) return launch_dconv_up_pack<G>(w, ws, ws_bytes, s);
-  else if constexpr (!std::is_void<UC>::value) return launch_uconv_pack<G, UC>(w, ws, ws_bytes, s);
-  else return REPO_OK;  // the 3-channel layers read the native weights
+  using R = Route<G>;
+  const size_t ws_have = ws ? ws_bytes : 0;
+  const UpPlan p = up_plan<G>(0, REPO_EPI_NONE, ws_have);
+  if (ws_have < (p.tcu_live ? p.total : p.need)) return REPO_E_WS_TOO_SMALL;
+  if (p.tcu_live)   // both packs: which kernel a later call takes depends on its epilogue and batch
+    if (const int rc = launch_tconv_up_pack(w, (char*)ws + p.tcu_off, s)) return rc;
+  if constexpr (kOn<typename R::UpBfScatter>)
+    if (p.base == UpEngine::BfScatter) return launch_buconv_pack<G, typename R::UpBfScatter>(w, ws, ws_bytes, s);
+  if constexpr (kOn<typename R::DirectUp>) return launch_dconv_up_pack<G>(w, ws, ws_bytes, s);
+  else if constexpr (kOn<typename R::UpScatter>) return launch_uconv_pack<G, typename R::UpScatter>(w, ws, ws_bytes, s);
+  else return REPO_OK;  // the merged gather engine reads the native weights
 }
 
 template <class G>
 static int conv_up_t(int64_t nimg, const float* small, const float* w, const float* bias, float* big, int epi,
                      const float* aux, int packed, void* ws, size_t ws_bytes, hipStream_t s) {
   if (nimg * (int64_t)G::CB * G::PB >= kMaxBufElems || nimg * (int64_t)G::CS * G::PS >= kMaxBufElems) return REPO_E_SHAPE;
-  using UC = typename UConf<G>::type;
-  using BC = typename BUConf<G>::type;
-  // the channel-quad mask is what the scatter kernels' drain reads (a pixel's four channels per item)
-  if (epi == REPO_EPI_MUL_CMASK && (kUpDirect<G> || std::is_void<UC>::value || G::CB % 4 != 0)) return REPO_E_BADARG;
-  if (epi == REPO_EPI_FILM_RELU && (kUpDirect<G> || std::is_void<UC>::value)) return REPO_E_BADARG;   // the scatter kernels' drains
-  if constexpr (kTconvUp<G>) {
-    const bool epi_ok = epi == REPO_EPI_NONE || epi == REPO_EPI_MUL_DRELU || epi == REPO_EPI_MUL_CMASK;   // the encoder backward's forms; ReLU / FiLM: the scatter kernel
-    if (buconv_on<G>() && epi_ok && nimg >= 4 && ws && ws_bytes >= conv_up_ws_bytes<G>()) {
-      char* pack = (char*)ws + conv_up_tcu_off<G>();
-      if (!packed) {
-        const int rc = launch_tconv_up_pack(w, pack, s);
-        if (rc) return rc;
-      }
+  using R = Route<G>;
+  // the channel-quad mask and FiLM are what the scatter kernels' drains read (a pixel's four channels per item)
+  if (epi == REPO_EPI_MUL_CMASK && (!kOn<typename R::UpScatter> || G::CB % 4 != 0)) return REPO_E_BADARG;
+  if (epi == REPO_EPI_FILM_RELU && !kOn<typename R::UpScatter>) return REPO_E_BADARG;
+  const size_t ws_have = ws ? ws_bytes : 0;
+  const UpPlan p = up_plan<G>(nimg, epi, ws_have);
+  if (ws_have < p.need) return REPO_E_WS_TOO_SMALL;
+  if constexpr (R::UpTconv)
+    if (p.engine == UpEngine::Tconv) {
+      char* pack = (char*)ws + p.tcu_off;
+      if (!packed)
+        if (const int rc = launch_tconv_up_pack(w, pack, s)) return rc;
       return launch_tconv_up(small, pack, bias, aux, big, nimg, epi, s);
     }
-  }
-  if constexpr (!std::is_void<BC>::value)
-    if (buconv_on<G>()) return launch_buconv_scatter<G, BC>(small, w, bias, aux, big, nimg, epi, packed, ws, ws_bytes, s);
-  if constexpr (kUpDirect<G>) {
-    return launch_dconv_up<G, typename UpDirect<G>::type>(small, w, bias, aux, big, nimg, epi, packed, ws, ws_bytes, s);
-  } else if constexpr (!std::is_void<UC>::value) {
-    return launch_uconv_scatter<G, UC>(small, w, bias, aux, big, nimg, epi, packed, ws, ws_bytes, s);
+  if constexpr (kOn<typename R::UpBfScatter>)
+    if (p.engine == UpEngine::BfScatter)
+      return launch_buconv_scatter<G, typename R::UpBfScatter>(small, w, bias, aux, big, nimg, epi, packed, ws, ws_bytes, s);
+  if constexpr (kOn<typename R::DirectUp>) {
+    return launch_dconv_up<G, typename R::DirectUp>(small, w, bias, aux, big, nimg, epi, packed, ws, ws_bytes, s);
+  } else if constexpr (kOn<typename R::UpScatter>) {
+    return launch_uconv_scatter<G, typename R::UpScatter>(small, w, bias, aux, big, nimg, epi, packed, ws, ws_bytes, s);
   } else {
-    // 3-channel outputs (encoder conv1 data-gradient, plain decoder conv4) and, in the 128 x 128 stack, the outputs
-    // whose class planes do not fit LDS: the four output parity classes read the same (J x J) input taps, so they
-    // are merged on M (4 * CB rows) in the gather engine of igemm.h
+    // UpEngine::Merged: 3-channel outputs (encoder conv1 data-gradient, plain decoder conv4) and, in the 128 x 128 stack,
+    // the outputs whose class planes do not fit LDS: the four output parity classes read the same (J x J) input taps, so
+    // they are merged on M (4 * CB rows) in the gather engine of igemm.h
     static_assert(G::KS % 2 == 0, "the gather engine pairs horizontally adjacent output pixels");
     ConvUpMergedOp<G, float, 0> op{small, w, bias, aux, big, (int)nimg, epi, nullptr, nullptr, nullptr, 0.f, 0.f};
     if constexpr (G::CB < 8) return launch_igemm<T32x256>(op, 4 * G::CB, nimg * (int64_t)op.NY * op.NX, 1, s);
@@ -659,64 +709,8 @@ static int conv_up_t(int64_t nimg, const float* small, const float* w, const flo
   }
 }
 
-template <class G>
-static int dwgrad_ips(int64_t nimg) {
-  using T = typename DTileFor<G>::Wgrad;
-  const long tiles = ((G::CS + T::BM - 1) / T::BM) * ((G::CB * G::KK + T::BN - 1) / T::BN);
-  long want = (DTileFor<G>::WGT + tiles - 1) / tiles;
-  long ips = (nimg + want - 1) / want;
-  const long min_ips = T::GI * ((G::PS >= 512) ? 1 : (G::PS >= 64 ? 2 : 4));
-  if (ips < min_ips) ips = min_ips;
-  ips = (ips + T::GI - 1) / T::GI * T::GI;
-  return (int)ips;
-}
-template <class G>
-static int dwgrad_splits(int64_t nimg) {
-  const long ips = dwgrad_ips<G>(nimg);
-  return (int)((nimg + ips - 1) / ips);
-}
-template <class G>
-static size_t wgrad_ws_bytes(int64_t nimg) {
-  return (size_t)dwgrad_splits<G>(nimg) * G::CS * (G::CB * G::KK + 1) * sizeof(float);
-}
-
-static void launch_conv_slab_reduce(const float* ws, int splits, int cs, int nw, float* dw, float* db, int accumulate,
-                                    hipStream_t s) {
-  const int total = cs * (nw + 1);
-  if (splits >= 64 && total <= 65536) {
-    hipLaunchKernelGGL(conv_slab_reduce_wave_kernel, dim3(cdiv(total, 64)), dim3(64 * SLAB_REDUCE_WAVES), 0, s, ws, splits, cs, nw, dw, db,
-                       accumulate, 0, 0, (float*)nullptr);
-  } else {
-    const int blocks = cdiv(total, 256) < 2048 ? cdiv(total, 256) : 2048;
-    hipLaunchKernelGGL(conv_slab_reduce_kernel, dim3(blocks), dim3(256), 0, s, ws, splits, cs, nw, dw, db, accumulate);
-  }
-}
-
-// The bf16x6 weight-gradient kernel (bwgrad.h) for the layers whose bands fill whole 16-k blocks reasonably (enc4's 2 x 2
-// planes would run 4 real k in a block of 16; the 3-channel layers are not MFMA-bound): tile BM x BN, waves, images per
-// chunk, small rows per band.  The split-K over image groups (slabs, reduce) is the fp32 kernel's.
-template <class G> struct BWgradFor { using type = NoBTile; };
-template <> struct BWgradFor<GDec3> { using type = WTile<64, 128, 1, 4, 1, 7>; };   // 531 -> 465 us (64 x 64 wave tiles: 551)
-template <> struct BWgradFor<GEnc3> { using type = WTile<64, 256, 1, 4, 1, 6>; };   // 215 -> 172-182 us
-// measured and left on the fp32 kernel: enc2 (31 x 31 planes: 343-445 us against 320) and dec2 (232-244 against 247) --
-// with one or two waves per SIMD the in-register split of the B fragments (44 dependent vector instructions per 8
-// elements) is not hidden behind 12 MFMAs
-template <class G> constexpr bool kBWgrad = !std::is_same<typename BWgradFor<G>::type, NoBTile>::value;
-
-// twgrad.h (both operands split at staging, `big` read through the LDS's transposing load): k-blocks per chunk, 0 = not
-// on this engine.  A PAIR of workgroups (the two row parities of the taps) owns the whole dw of its images: images per
-// split = ceil(nimg / 128), one slab per pair.
-template <class G> constexpr int kTWgradNBK = 0;
-#ifndef TW_DISABLE   // A/B builds (tools/build_variant.sh): the previous engines
-template <> constexpr int kTWgradNBK<GDec3> = 2;
-template <> constexpr int kTWgradNBK<GEnc2> = 2;
-#endif
-// staging waves: 8 where the multiplying waves (4 taps: 64 accumulator registers) fit three waves per SIMD
-template <class G> constexpr int kTWgradNPW = 4;
-template <> constexpr int kTWgradNPW<GEnc2> = 8;
-static int twgrad_ips(int64_t nimg) { return (int)((nimg + 127) / 128); }
-static int twgrad_splits(int64_t nimg) { return (int)((nimg + twgrad_ips(nimg) - 1) / twgrad_ips(nimg)); }
-
+// ---- weight gradient.  Workspace: [one slab per split (room for the larger of the engines' sets: the engine is a
+// thread-local switch) | the channel sums' partials for dbias_big where the engine does not produce them]
 static inline int chansum_splits(int64_t nimg, int64_t C, int64_t P) {
   long want = (4096 + C - 1) / C;
   long min_imgs = (8192 + P - 1) / P;
@@ -739,69 +733,84 @@ static int channel_sum_launch(int64_t nimg, int64_t C, int64_t P, const float* x
   return REPO_OK;
 }
 
-// slabs of the weight gradient (the larger of the engines' sets: the engine is a thread-local switch), then the channel
-// sums' partials for dbias_big where the engine does not produce them
-template <class G>
-static size_t wgrad_ws_slabs(int64_t nimg) {
-  size_t b = wgrad_ws_bytes<G>(nimg);
-  if constexpr (kTWgradNBK<G> > 0) {
-    const size_t t = (size_t)twgrad_splits(nimg) * TWGeo<G, kTWgradNBK<G>, kTWgradNPW<G>>::SLAB * sizeof(float);
-    if (t > b) b = t;
+enum class WgradEngine { Transposing, Bf16, Fp32 };
+struct WgradPlan {
+  WgradEngine engine;
+  int ips, splits;      // images per split, splits (= slabs)
+  int slab_floats;      // one slab
+  bool dbig_in_slabs;   // the channel sums of `big` ride along (behind each slab) and leave through the slab reduce
+  bool wave_reduce;     // conv_slab_reduce_wave_kernel (many splits, few outputs) or conv_slab_reduce_kernel
+  size_t chan_off;      // offset of the separate channel-sum pass's partials
+  size_t need;
+};
+template <class G, class BigT>
+static WgradPlan wgrad_plan(int64_t nimg, bool wants_dbig) {
+  using R = Route<G>;
+  using T = typename R::Wgrad;
+  constexpr bool kFloat = std::is_same<BigT, float>::value;
+  const long tiles = ((G::CS + T::BM - 1) / T::BM) * ((G::CB * G::KK + T::BN - 1) / T::BN);
+  const long want = (R::WGT + tiles - 1) / tiles;
+  const long min_ips = T::GI * ((G::PS >= 512) ? 1 : (G::PS >= 64 ? 2 : 4));
+  const long ips = (std::max((long)(nimg + want - 1) / want, min_ips) + T::GI - 1) / T::GI * T::GI;
+  constexpr int row = G::CS * (G::CB * G::KK + 1);
+  WgradPlan p{WgradEngine::Fp32, (int)ips, (int)((nimg + ips - 1) / ips), row, false, false, 0, 0};
+  p.wave_reduce = p.splits >= 64 && row <= 65536;
+  size_t slabs = (size_t)p.splits * row * sizeof(float);
+  if constexpr (kOn<typename R::WgradBf> && kFloat) {
+    static_assert(T::GI % R::WgradBf::GI == 0, "images per split: a multiple of both kernels' chunks");
+    if (t_bconv_enabled) p.engine = WgradEngine::Bf16;
   }
-  return (b + 255) & ~(size_t)255;
-}
-template <class G>
-static size_t wgrad_ws_total(int64_t nimg) {
-  return wgrad_ws_slabs<G>(nimg) + (size_t)chansum_splits(nimg, G::CB, G::PB) * G::CB * sizeof(float);
+  if constexpr (R::TwNBK > 0) {
+    using TG = TWGeo<G, R::TwNBK, R::TwNPW>;
+    const int tips = (int)((nimg + 127) / 128), tsplits = (int)((nimg + tips - 1) / tips);
+    slabs = std::max(slabs, (size_t)tsplits * TG::SLAB * sizeof(float));
+    // where the taps reach every row and column of `big` (decoder conv3; not the 31 x 31 planes of encoder conv2, whose
+    // last row and column no window touches) every element is staged exactly once and its channel sums ride along
+    constexpr bool covers = R::TwDbig && G::HB == 2 * (G::HS - 1) + G::KS;
+    if (kFloat && t_bconv_enabled) p = WgradPlan{WgradEngine::Transposing, tips, tsplits, TG::SLAB, covers && wants_dbig, true, 0, 0};
+  }
+  p.chan_off = round256(slabs);
+  p.need = p.chan_off + (size_t)chansum_splits(nimg, G::CB, G::PB) * G::CB * sizeof(float);
+  return p;
 }
 
 template <class G, class BigT>
 static int conv_wgrad_t(int64_t nimg, const float* small, const BigT* big, float* dw, float* db, float* dbig,
                         int accumulate, void* ws, size_t ws_bytes, hipStream_t s) {
   if (nimg * (int64_t)G::CB * G::PB >= kMaxBufElems || nimg * (int64_t)G::CS * G::PS >= kMaxBufElems) return REPO_E_SHAPE;
-  if (!ws || ws_bytes < wgrad_ws_total<G>(nimg)) return REPO_E_WS_TOO_SMALL;
-  const int dips = dwgrad_ips<G>(nimg), dsplits = dwgrad_splits<G>(nimg);
-  WgradArgs a{small, big, (float*)ws, (int)nimg, dips, db != nullptr,
+  using R = Route<G>;
+  constexpr bool kFloat = std::is_same<BigT, float>::value;
+  const WgradPlan p = wgrad_plan<G, BigT>(nimg, dbig != nullptr);
+  if (!ws || ws_bytes < p.need) return REPO_E_WS_TOO_SMALL;
+  WgradArgs a{small, big, (float*)ws, (int)nimg, p.ips, db != nullptr,
               (unsigned)(nimg * G::CS * G::PS * sizeof(float)), (unsigned)(nimg * G::CB * G::PB * sizeof(BigT))};
-  int rc;
-  if constexpr (kTWgradNBK<G> > 0 && std::is_same<BigT, float>::value) {
-    if (t_bconv_enabled) {
-      using TG = TWGeo<G, kTWgradNBK<G>, kTWgradNPW<G>>;
-      const int tsplits = twgrad_splits(nimg);
-      a.imgs_per_split = twgrad_ips(nimg);
-      // where the taps reach every row and column of `big` (decoder conv3; not the 31 x 31 planes of encoder conv2, whose
-      // last row and column no window touches) every element is staged exactly once and its channel sums ride along
-#ifdef TW_NO_DBIG   // A/B builds: the separate channel-sum pass
-      constexpr bool covers = false;
-#else
-      constexpr bool covers = G::HB == 2 * (G::HS - 1) + G::KS;
-#endif
-      a.want_dbig = covers && dbig != nullptr;
-      rc = launch_tconv_wgrad<G, kTWgradNBK<G>, kTWgradNPW<G>>(a, tsplits, s);
-      if (rc) return rc;
-      hipLaunchKernelGGL(conv_slab_reduce_wave_kernel, dim3(cdiv(TG::SLAB, 64)), dim3(64 * SLAB_REDUCE_WAVES), 0, s, (const float*)ws, tsplits,
-                         G::CS, G::CB * G::KK, dw, db, accumulate, G::KK, G::CB, covers ? dbig : nullptr);
-      REPO_CHECK_LAUNCH();
-      if (!covers && dbig)
-        return channel_sum_launch(nimg, G::CB, G::PB, big, dbig, accumulate, (float*)((char*)ws + wgrad_ws_slabs<G>(nimg)), s);
-      return REPO_OK;
-    }
-  }
-  if constexpr (kBWgrad<G> && std::is_same<BigT, float>::value) {
-    static_assert(DTileFor<G>::Wgrad::GI % BWgradFor<G>::type::GI == 0, "images per split: a multiple of both kernels' chunks");
-    if (t_bconv_enabled) rc = launch_bconv_wgrad<G, typename BWgradFor<G>::type>(a, dsplits, s);
-    else rc = launch_dconv_wgrad<G, BigT, typename DTileFor<G>::Wgrad>(a, dsplits, s);
-  } else {
-    rc = launch_dconv_wgrad<G, BigT, typename DTileFor<G>::Wgrad>(a, dsplits, s);
+  a.want_dbig = p.dbig_in_slabs;
+  int rc = REPO_E_BADARG;
+  switch (p.engine) {
+    case WgradEngine::Transposing:
+      if constexpr (R::TwNBK > 0 && kFloat) rc = launch_tconv_wgrad<G, R::TwNBK, R::TwNPW>(a, p.splits, s);
+      break;
+    case WgradEngine::Bf16:
+      if constexpr (kOn<typename R::WgradBf> && kFloat) rc = launch_bconv_wgrad<G, typename R::WgradBf>(a, p.splits, s);
+      break;
+    case WgradEngine::Fp32: rc = launch_dconv_wgrad<G, BigT, typename R::Wgrad>(a, p.splits, s); break;
   }
   if (rc) return rc;
-  launch_conv_slab_reduce((const float*)ws, dsplits, G::CS, G::CB * G::KK, dw, db, accumulate, s);
+  if (p.wave_reduce) {
+    // the transposing engine's slabs are [tap][row][channel] (+ db, + the channel sums of `big`): the kernel's tkk / tcb
+    const bool tw = p.engine == WgradEngine::Transposing;
+    hipLaunchKernelGGL(conv_slab_reduce_wave_kernel, dim3(cdiv(p.slab_floats, 64)), dim3(64 * SLAB_REDUCE_WAVES), 0, s,
+                       (const float*)ws, p.splits, G::CS, G::CB * G::KK, dw, db, accumulate, tw ? G::KK : 0, tw ? G::CB : 0,
+                       p.dbig_in_slabs ? dbig : (float*)nullptr);
+  } else {
+    const int blocks = cdiv(p.slab_floats, 256) < 2048 ? cdiv(p.slab_floats, 256) : 2048;
+    hipLaunchKernelGGL(conv_slab_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)ws, p.splits, G::CS, G::CB * G::KK, dw, db,
+                       accumulate);
+  }
   REPO_CHECK_LAUNCH();
-  if (dbig) {
-    if constexpr (std::is_same<BigT, float>::value)
-      return channel_sum_launch(nimg, G::CB, G::PB, big, dbig, accumulate, (float*)((char*)ws + wgrad_ws_slabs<G>(nimg)), s);
-    else
-      return REPO_E_BADARG;
+  if (dbig && !p.dbig_in_slabs) {
+    if constexpr (kFloat) return channel_sum_launch(nimg, G::CB, G::PB, big, dbig, accumulate, (float*)((char*)ws + p.chan_off), s);
+    else return REPO_E_BADARG;
   }
   return REPO_OK;
 }
@@ -856,10 +865,7 @@ extern "C" int repo_conv_down(int layer, int64_t nimg, const void* big, int big_
 
 extern "C" size_t repo_conv_down_workspace_bytes(int layer, int64_t nimg) {
   if (nimg <= 0) return 0;
-  // (the frame type is not known here: room for whichever of the float / uint8 variants needs more)
-  REPO_LAYER_SWITCH(layer, return (std::max(bconv_down_on<G, float>(nimg) ? bconv_pack_bytes<G, float>() : 0,
-                                            bconv_down_on<G, uint8_t>(nimg) ? bconv_pack_bytes<G, uint8_t>() : 0) +
-                                   (size_t)std::max(conv_down_tiles<G, float>(nimg), conv_down_tiles<G, uint8_t>(nimg)) * G::CS * sizeof(float)))
+  REPO_LAYER_SWITCH(layer, return (conv_down_ws_bytes<G>(nimg)))
 }
 
 extern "C" int repo_debug_bconv(int enable) {
@@ -869,7 +875,7 @@ extern "C" int repo_debug_bconv(int enable) {
 }
 
 extern "C" size_t repo_conv_up_workspace_bytes(int layer) {
-  REPO_LAYER_SWITCH(layer, return (conv_up_ws_bytes<G>()))
+  REPO_LAYER_SWITCH(layer, return (up_plan<G>(0, REPO_EPI_NONE, 0).total))
 }
 
 extern "C" int repo_conv_up_pack(int layer, const float* w, void* ws, size_t ws_bytes, hipStream_t stream) {
@@ -892,7 +898,7 @@ extern "C" int repo_conv_up(int layer, int64_t nimg, const float* small, const f
 
 extern "C" size_t repo_conv_wgrad_workspace_bytes(int layer, int64_t nimg) {
   if (nimg <= 0) return 0;
-  REPO_LAYER_SWITCH(layer, return (wgrad_ws_total<G>(nimg)))
+  REPO_LAYER_SWITCH(layer, return (wgrad_plan<G, float>(nimg, false).need))
 }
 
 extern "C" int repo_conv_wgrad(int layer, int64_t nimg, const float* small, const void* big, int big_is_u8,
@@ -932,29 +938,23 @@ static int decoder_out_nll_t(int64_t nimg, const float* h3, const float* w, cons
   float* chan = (float*)ws + nparts;
   NllArgs a{h3, w, bias, target, recon, dpre, mask4, (float*)ws, grad_scale, (int)nimg,
             (unsigned)(nimg * G::CS * G::PS * sizeof(float))};
-  // the bf16x6 kernel (bdec4.h) unless repo_debug_bconv(0) asks for the fp32-MFMA twin
-  if (t_bconv_enabled) {
-    a.chan_partials = dbias ? chan : nullptr;
-    hipLaunchKernelGGL((bdec4_nll_kernel<TgtT>), dim3(nparts), dim3(256), 0, stream, a);
-  } else {
-    hipLaunchKernelGGL((dconv_dec4_nll_kernel<TgtT>), dim3(nparts), dim3(256), 0, stream, a);
-  }
+  // ONE decision: the bf16x6 kernel (bdec4.h), whose per-channel partials are the bias gradient's, or -- repo_debug_bconv(0)
+  // -- the fp32-MFMA twin with a channel-sum pass over dpre
+  const bool bf = t_bconv_enabled != 0;
+  a.chan_partials = bf && dbias ? chan : nullptr;
+  if (bf) hipLaunchKernelGGL((bdec4_nll_kernel<TgtT>), dim3(nparts), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((dconv_dec4_nll_kernel<TgtT>), dim3(nparts), dim3(256), 0, stream, a);
   REPO_CHECK_LAUNCH();
   if (loss_sum) {
-    hipLaunchKernelGGL(partial_sum_kernel, dim3(1), dim3(1024), 0, stream, (const float*)ws, nparts,
-                       loss_sum, 0);
+    hipLaunchKernelGGL(partial_sum_kernel, dim3(1), dim3(1024), 0, stream, (const float*)ws, nparts, loss_sum, 0);
     REPO_CHECK_LAUNCH();
   }
-  if (dbias) {   // the output layer's bias gradient = the channel sums of dpre
-    if (t_bconv_enabled) {
-      hipLaunchKernelGGL(partial_sum_rows_kernel, dim3(3), dim3(256), 0, stream, (const float*)chan, nparts, dbias, grad_scale,
-                         accumulate_dbias);
-      REPO_CHECK_LAUNCH();
-    } else {
-      if (!dpre) return REPO_E_BADARG;
-      return channel_sum_launch(nimg, G::CB, G::PB, dpre, dbias, accumulate_dbias, chan, stream);
-    }
-  }
+  if (!dbias) return REPO_OK;
+  // the output layer's bias gradient = the channel sums of dpre
+  if (!bf) return dpre ? channel_sum_launch(nimg, G::CB, G::PB, dpre, dbias, accumulate_dbias, chan, stream) : REPO_E_BADARG;
+  hipLaunchKernelGGL(partial_sum_rows_kernel, dim3(3), dim3(256), 0, stream, (const float*)chan, nparts, dbias, grad_scale,
+                     accumulate_dbias);
+  REPO_CHECK_LAUNCH();
   return REPO_OK;
 }
 
