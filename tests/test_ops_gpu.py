@@ -9,7 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.util import log, relerr, rnd
+from tests.util import CONV_ENGINE_KERNELS, has, log, relerr, rnd, traced
 
 pytestmark = pytest.mark.gpu
 
@@ -354,18 +354,38 @@ def test_conv_up_gather_form_many_images_per_workgroup(ops, nimg):
     assert torch.equal(a, m)
 
 
-@pytest.mark.parametrize("layer,kind", [(5, "down"), (1, "down"), (2, "down"), (3, "down"), (4, "down"), (5, "up"), (1, "up"), (2, "up"),
-                                        (3, "up"), (4, "up"), (5, "wgrad"), (2, "wgrad"), (1, "wgrad")])
-def test_bf16x6_conv_kernels_match_fp64_and_the_fp32_kernels(ops, layer, kind):
+# (layer, pass, images, the kernel a device trace must show with repo_debug_bconv on).  41 images fill several pixel tiles
+# and straddle images; where conv.hip's plans hand 41 images of that call to another engine, the count that keeps the
+# call on the kernel the case is about: decoder conv3's plain data gradient goes to tconv_down.h from 32 images (29),
+# encoder conv4's 2 x 2 planes stay on the latency tiles up to 128 images (150); encoder conv2's plain data gradient goes
+# to tconv_up.h from 4 images, so its buconv.h case keeps the 41 images and takes the epilogue that stays there (ReLU with
+# bias: the decoder's forward form).  Those engines have cases of their own (-tcd, -tcu); both weight gradients on the
+# transposing engine are twgrad.h's (decoder conv3 on bwgrad.h is shadowed by it in the default build).
+_BF16X6_CASES = [
+    pytest.param(5, "down", 29, "bconv_down_kernel", id="5-down"), pytest.param(1, "down", 41, "bconv_down_kernel", id="1-down"),
+    pytest.param(2, "down", 41, "bconv_down_kernel", id="2-down"), pytest.param(3, "down", 150, "bconv_down_kernel", id="3-down"),
+    pytest.param(4, "down", 41, "bconv_down_kernel", id="4-down"), pytest.param(5, "up", 41, "buconv_scatter_kernel", id="5-up"),
+    pytest.param(1, "up", 41, "buconv_scatter_kernel", id="1-up"), pytest.param(2, "up", 41, "buconv_scatter_kernel", id="2-up"),
+    pytest.param(3, "up", 41, "buconv_scatter_kernel", id="3-up"), pytest.param(4, "up", 41, "buconv_scatter_kernel", id="4-up"),
+    pytest.param(5, "wgrad", 41, "tconv_wgrad_kernel", id="5-wgrad"), pytest.param(2, "wgrad", 41, "bconv_wgrad_kernel", id="2-wgrad"),
+    pytest.param(1, "wgrad", 41, "tconv_wgrad_kernel", id="1-wgrad"),
+    pytest.param(5, "down", 41, "tconv_down_kernel", id="5-down-tcd"), pytest.param(1, "up", 41, "tconv_up_kernel", id="1-up-tcu"),
+]
+_BF16X6_FP32_TWIN = {"down": "dconv_down_kernel", "up": "uconv_scatter_kernel", "wgrad": "dconv_wgrad_kernel"}
+
+
+@pytest.mark.parametrize("layer,kind,nimg,kernel", _BF16X6_CASES)
+def test_bf16x6_conv_kernels_match_fp64_and_the_fp32_kernels(ops, layer, kind, nimg, kernel):
     """The bf16x6 conv kernels (csrc/bconv.h: decoder conv3 / conv2 data gradients, encoder conv2 / conv3 / conv4 forward;
-    csrc/buconv.h: decoder conv3 / conv2 forward, encoder conv2 / conv3 / conv4 data gradients; csrc/bwgrad.h: decoder conv3
-    and encoder conv3 weight gradients) against fp64 at a batch that fills several
+    csrc/buconv.h: decoder conv3 / conv2 forward, encoder conv2 / conv3 / conv4 data gradients; csrc/bwgrad.h: encoder conv3's
+    weight gradient; csrc/twgrad.h: decoder conv3's and encoder conv2's; csrc/tconv_down.h and csrc/tconv_up.h: the -tcd / -tcu
+    cases) against fp64 at a batch that fills several
     pixel tiles and straddles images -- and against the fp32-MFMA kernel of the same layer on the SAME operands
     (repo_debug_bconv(0)): the error relative to sum |a||b| may not exceed that kernel's by more than 25 % (measured: at or
-    below it), i.e. the six-product split is an fp32-accurate way of feeding the bf16 pipe, not a reduced precision."""
+    below it), i.e. the six-product split is an fp32-accurate way of feeding the bf16 pipe, not a reduced precision.  A
+    device trace shows that the kernel the case names ran, and its fp32 twin with the switch off."""
     from repo_amd._lib import lib
 
-    nimg = 41
     big, small, w, rs = _layer_tensors(ops, layer, nimg, 900 + layer)
     big[::3] *= 25.0
     small[::3] *= 25.0
@@ -388,13 +408,21 @@ def test_bf16x6_conv_kernels_match_fp64_and_the_fp32_kernels(ops, layer, kind):
         want = pad(F.conv_transpose2d(small.double(), w.double(), None, stride=2))
         mag = pad(F.conv_transpose2d(small.double().abs(), w.double().abs(), None, stride=2)) + 1e-30
         run = lambda: ops.conv_up(layer, dev(small), dev(w), None, epi=ops.EPI_NONE)  # noqa: E731
+        if (layer, kernel) == (1, "buconv_scatter_kernel"):   # ReLU with bias: the |bias| joins the magnitude
+            bias = rnd(rs, big.shape[1])
+            want = F.relu(want + bias.double().view(1, -1, 1, 1))
+            mag = mag + bias.double().abs().view(1, -1, 1, 1)
+            run = lambda: ops.conv_up(layer, dev(small), dev(w), dev(bias), epi=ops.EPI_RELU)  # noqa: E731
     errs = {}
     for engine in (1, 0):
         prev = lib().repo_debug_bconv(engine)
         try:
-            got = run()
+            got, names = traced(run)
         finally:
             lib().repo_debug_bconv(prev)
+        ran = kernel if engine else _BF16X6_FP32_TWIN[kind]
+        assert has(names, rf"\b{ran}\b"), (layer, kind, nimg, engine, names)
+        assert not any(has(names, rf"\b{k}\b") for k in set(CONV_ENGINE_KERNELS) - {ran}), (layer, kind, nimg, engine, names)
         assert relerr(got, want) < TOL
         errs[engine] = float(((got.double().cpu() - want).abs() / (mag + 1e-30)).max())
     log(f"bf16x6 conv layer {layer} {kind}: max |err| / sum|a||b|  bf16x6 {errs[1]:.2e}  fp32 MFMA {errs[0]:.2e}")

@@ -19,7 +19,7 @@ import torch
 
 from oracle import fixtures as fx
 from oracle import repo_oracle as ro
-from tests.util import l2err, log, relerr
+from tests.util import has, l2err, log, relerr, traced
 
 FTOL = 1e-5
 GTOL = 1e-4
@@ -137,24 +137,6 @@ def g64(rs, *shape, scale=1.0):
 
 def dev(t):
     return t.detach().float().cuda().contiguous()
-
-
-def traced(fn):
-    """(fn(), names of the device kernels it launched).  Every traced call launches HIP kernels: a trace that lists none
-    cannot confirm an engine, and fails the case."""
-    from torch.profiler import ProfilerActivity, profile
-
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names = sorted({e.name for e in prof.events() if "kernel" in e.name.lower() and "hipLaunch" not in e.name})
-    assert names, "the device trace lists no HIP kernels: the engine that ran cannot be confirmed"
-    return out, names
-
-
-def has(names, pattern):
-    return any(re.search(pattern, n) for n in names)
 
 
 def row_tiles(names, direction):

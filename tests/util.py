@@ -1,4 +1,5 @@
 import os
+import re
 
 import numpy as np
 import torch
@@ -30,3 +31,29 @@ def l2err(got, want):
 
 def rnd(rs, *shape, scale=1.0):
     return torch.from_numpy((rs.standard_normal(shape) * scale).astype(np.float32))
+
+
+def traced(fn):
+    """(fn(), names of the device kernels it launched).  Every traced call launches HIP kernels: a trace that lists none
+    cannot confirm an engine, and fails the case."""
+    from torch.profiler import ProfilerActivity, profile
+
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        out = fn()
+        torch.cuda.synchronize()
+    names = sorted({e.name for e in prof.events() if "kernel" in e.name.lower() and "hipLaunch" not in e.name})
+    assert names, "the device trace lists no HIP kernels: the engine that ran cannot be confirmed"
+    return out, names
+
+
+def has(names, pattern):
+    return any(re.search(pattern, n) for n in names)
+
+
+# One kernel per conv engine (csrc/conv.hip's plans pick exactly one of them per call), and the kernels that finish a weight
+# gradient.  The only list of these names in the tests: a new engine is added here.
+CONV_ENGINE_KERNELS = ("dconv_down_kernel", "bconv_down_kernel", "tconv_down_kernel", "uconv_scatter_kernel", "buconv_scatter_kernel",
+                       "dconv_up_kernel", "tconv_up_kernel", "igemm_kernel", "dconv_wgrad_kernel", "bconv_wgrad_kernel",
+                       "tconv_wgrad_kernel")
+CONV_REDUCE_KERNELS = ("conv_slab_reduce_kernel", "conv_slab_reduce_wave_kernel", "channel_sum_kernel")
