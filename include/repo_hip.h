@@ -33,7 +33,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-#define REPO_ABI_VERSION 8
+#define REPO_ABI_VERSION 9
 
 #define REPO_OK 0
 #define REPO_E_BADARG (-1)
@@ -67,6 +67,14 @@ typedef struct ihipStream_t* hipStream_t;
                                 bias_div, ldaux = 2 C): the modulation is an epilogue, the pre-FiLM tensor is never
                                 written; the backward pass recovers it from the output (repo_film_bwd_h)             */
 
+/* Dense activation (ABI v9): config.dense_activation_function of the reference, which builds every dense layer of the
+ * RSSM (models/rssm.py:24, act_fn = getattr(F, activation_function)), the reward head (models/decoder.py:178-195) and
+ * the value head (models/actor_critic.py:9-26) with it.  The `_act` entry points below take it as their LAST argument;
+ * the entry points without the suffix are the same calls with REPO_ACT_ELU.  Any other value: REPO_E_BADARG.  Each
+ * fused kernel is compiled once per activation (no run-time branch in its epilogues); shapes, saved tensors and
+ * workspace sizes do not depend on it, and the backward must be given the activation of its forward. */
+#define REPO_ACT_ELU 0  /* F.elu(alpha=1) */
+#define REPO_ACT_RELU 1 /* F.relu         */
 int repo_abi_version(void);
 const char* repo_strerror(int code);
 /* REPO_OK if HIP device `device` is gfx950 (MI355X), REPO_E_ARCH if it is another architecture, REPO_E_BADARG
@@ -288,6 +296,16 @@ int repo_rssm_observe_fwd(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd
                           float* prior_std, float* post_mean, float* post_std, float* xsa, float* e,
                           float* gates, float* hp, float* hq, float* eemb, int prior_only, unsigned* status,
                           void* ws, size_t ws_bytes, hipStream_t stream);
+/* ABI v9: the scan with act_fn = `act` (rssm.py:24,37,43,55: e, the prior hidden hp and the posterior hidden hq). */
+int repo_rssm_observe_fwd_act(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t E,
+                              const float* const* params, const float* prev_belief,
+                              const float* prev_state, const float* actions, const float* nonterms,
+                              const float* embeds, const float* eps_prior, const float* eps_post,
+                              uint64_t noise_seed, uint64_t noise_offset,
+                              float min_std, float* featx, float* prior_state, float* prior_mean,
+                              float* prior_std, float* post_mean, float* post_std, float* xsa, float* e,
+                              float* gates, float* hp, float* hq, float* eemb, int prior_only, unsigned* status,
+                              void* ws, size_t ws_bytes, hipStream_t stream, int act);
 
 /* The prior head (fc_embed_belief_prior, fc_state_prior, softplus + sample: rssm.py:42-50) of ALL T steps at once.
  * It depends on belief_t only, i.e. it is off the recurrence: repo_rssm_observe_fwd(prior_only = 2) leaves it out of
@@ -300,6 +318,11 @@ int repo_rssm_prior_head(int64_t T, int64_t B, int64_t D, int64_t Hd, int64_t S,
                          const float* featx, const float* eps_prior, uint64_t noise_seed, uint64_t noise_offset,
                          float min_std, float* hp, float* prior_state, float* prior_mean, float* prior_std, void* ws,
                          size_t ws_bytes, hipStream_t stream);
+/* ABI v9: hp = act(fc_embed_belief_prior(belief)) (rssm.py:43). */
+int repo_rssm_prior_head_act(int64_t T, int64_t B, int64_t D, int64_t Hd, int64_t S, const float* const* params,
+                             const float* featx, const float* eps_prior, uint64_t noise_seed, uint64_t noise_offset,
+                             float min_std, float* hp, float* prior_state, float* prior_mean, float* prior_std,
+                             void* ws, size_t ws_bytes, hipStream_t stream, int act);
 
 /* Reverse scan (BPTT) + deferred weight gradients.  Upstream gradients (each nullable):
  * dfeat (T,B,D+S) w.r.t. featx[1:], dprior_state, dpm, dps, dqm, dqs (T,B,S) w.r.t. the
@@ -324,9 +347,22 @@ int repo_rssm_observe_bwd(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd
                           float* const* dparams, float* dembeds, float* dprev_belief,
                           float* dprev_state, int accumulate, unsigned* status, void* ws, size_t ws_bytes,
                           hipStream_t stream);
+/* ABI v9: autograd through act_fn = `act` (the derivative is taken from the saved e, hp, hq of
+ * repo_rssm_observe_fwd_act / repo_rssm_prior_head_act called with the same `act`; model_loss.backward(), repo.py:88). */
+int repo_rssm_observe_bwd_act(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t E,
+                              const float* const* params, const float* nonterms, const float* embeds,
+                              const float* eps_prior, const float* eps_post, uint64_t noise_seed,
+                              uint64_t noise_offset, float min_std,
+                              const float* featx, const float* prior_std, const float* post_std,
+                              const float* xsa, const float* e, const float* gates, const float* hp,
+                              const float* hq, const float* dfeat, const float* dprior_state,
+                              const float* dpm, const float* dps, const float* dqm, const float* dqs,
+                              float* const* dparams, float* dembeds, float* dprev_belief,
+                              float* dprev_state, int accumulate, unsigned* status, void* ws, size_t ws_bytes,
+                              hipStream_t stream, int act);
 
-/* ------------------------------------------------------------------ ELU-MLP heads
- * n_layers nn.Linear layers, ELU between, last layer linear (RewardModel / ValueModel:
+/* ------------------------------------------------------------------ MLP heads
+ * n_layers nn.Linear layers, ELU between (the `_act` forms: ELU or ReLU), last layer linear (RewardModel / ValueModel:
  * 4 layers, out_dim 1, models/decoder.py:189-195, models/actor_critic.py:20-26; ActorModel
  * trunk: 5 layers, out_dim 2A, models/actor_critic.py:76-82).  Input rows are [belief|state]
  * (the torch.cat of the reference is a row of the caller's feature buffer, ld = ldx).
@@ -340,6 +376,12 @@ size_t repo_mlp_fwd_workspace_bytes(int64_t rows, int64_t in_dim, int64_t hidden
 int repo_mlp_fwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers,
                  const float* x, int64_t ldx, const float* const* params, float* const* hidden_out,
                  float* out, int64_t ldo, void* ws, size_t ws_bytes, hipStream_t stream);
+/* ABI v9: act_fn = `act` between the layers (RewardModel.forward, models/decoder.py:189-195, and ValueModel.forward,
+ * models/actor_critic.py:20-26, with config.dense_activation_function; ActorModel(activation_function=...),
+ * models/actor_critic.py:76-82). */
+int repo_mlp_fwd_act(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers,
+                     const float* x, int64_t ldx, const float* const* params, float* const* hidden_out,
+                     float* out, int64_t ldo, void* ws, size_t ws_bytes, hipStream_t stream, int act);
 /* dparams NULL: frozen weights (FreezeParameters, dreamer.py:306-317); dx NULL: detached input.
  * dout_w (ABI v8, nullable; out_dim == 1, lddout == 1, dparams and dx given): TWO upstream gradients through ONE reverse
  * chain -- dx is the input gradient of `dout` over all rows, dparams the weight gradients of `dout_w` over the first
@@ -355,6 +397,12 @@ int repo_mlp_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, 
                  const float* const* hidden_acts, const float* dout, int64_t lddout,
                  float* const* dparams, int accumulate_w, float* dx, int64_t lddx, int accumulate_dx,
                  const float* dout_w, int64_t rows_w, void* ws, size_t ws_bytes, hipStream_t stream);
+/* ABI v9: the reverse chain of repo_mlp_fwd_act(act) (reward / value losses' backward, dreamer.py:287,357,373). */
+int repo_mlp_bwd_act(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers,
+                     const float* x, int64_t ldx, const float* const* params,
+                     const float* const* hidden_acts, const float* dout, int64_t lddout,
+                     float* const* dparams, int accumulate_w, float* dx, int64_t lddx, int accumulate_dx,
+                     const float* dout_w, int64_t rows_w, void* ws, size_t ws_bytes, hipStream_t stream, int act);
 
 /* Actor distribution head (models/actor_critic.py:84-87,89-102): raw (rows,2A) ->
  * mean = mean_scale*tanh(raw_m/mean_scale), std = softplus(raw_s+init_std)+min_std.
@@ -399,6 +447,19 @@ int repo_rssm_imagine_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t H
                           float* prior_std, float* a_hidden, int64_t a_layer_rows, float* a_raw,
                           float* a_mean, float* a_std, float* xsa, float* e, float* gates, float* hp,
                           void* ws, size_t ws_bytes, hipStream_t stream);
+/* ABI v9: `act` is the activation of the RSSM part of a step only (fc_embed_state_action and the prior hidden,
+ * rssm.py:159,163).  The ACTOR TRUNK inside the rollout stays ELU: the reference passes dense_activation_function
+ * positionally into ActorModel's `dist` slot (dreamer.py:99-105), so the actor is always built with its default. */
+int repo_rssm_imagine_fwd_act(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S,
+                              int n_actor_layers, const float* const* rssm_params,
+                              const float* const* actor_params, const float* belief0, const float* state0,
+                              const float* cond, int64_t C,
+                              const float* eps_act, const float* eps_prior, uint64_t noise_seed,
+                              uint64_t noise_offset, float min_std, float a_min_std,
+                              float a_init_std, float a_mean_scale, float* featx, float* prior_mean,
+                              float* prior_std, float* a_hidden, int64_t a_layer_rows, float* a_raw,
+                              float* a_mean, float* a_std, float* xsa, float* e, float* gates, float* hp,
+                              void* ws, size_t ws_bytes, hipStream_t stream, int act);
 /* Reverse pass with frozen world-model weights: dfeat (Hm,N,D+S) is the gradient w.r.t.
  * featx[1:] (from the heads and the entropy term), dprior_mean/std nullable.  Emits
  * d_araw (Hm*N,2A), the gradient at the actor trunk's output of every step (the caller
@@ -414,6 +475,16 @@ int repo_rssm_imagine_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t H
                           const float* hp, const float* dfeat, const float* dprior_mean,
                           const float* dprior_std, float* d_araw, float* dfeat0, void* ws,
                           size_t ws_bytes, hipStream_t stream);
+/* ABI v9: the reverse pass of repo_rssm_imagine_fwd_act(act) (actor_loss.backward(), dreamer.py:357). */
+int repo_rssm_imagine_bwd_act(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t C,
+                              const float* const* rssm_params, const float* eps_act,
+                              const float* eps_prior, uint64_t noise_seed, uint64_t noise_offset,
+                              float min_std, float a_min_std, float a_mean_scale,
+                              const float* featx, const float* prior_std, const float* a_mean,
+                              const float* a_std, const float* xsa, const float* e, const float* gates,
+                              const float* hp, const float* dfeat, const float* dprior_mean,
+                              const float* dprior_std, float* d_araw, float* dfeat0, void* ws,
+                              size_t ws_bytes, hipStream_t stream, int act);
 
 /* ------------------------------------------------------------------ losses and regularisers
  * All reductions use repo_reduce_workspace_bytes() of scratch and write device scalars

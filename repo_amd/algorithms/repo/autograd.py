@@ -60,34 +60,34 @@ def decoder_apply(mod, belief, state):
 
 class _MlpFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, *params):
+    def forward(ctx, feat, act, *params):
         p = _det(params)
-        out, hid = ops.mlp_fwd(p, feat)
-        ctx.feat, ctx.p, ctx.hid, ctx.dbg = feat, p, hid, ops.debug_snapshot()
+        out, hid = ops.mlp_fwd(p, feat, act=act)
+        ctx.feat, ctx.p, ctx.hid, ctx.dbg, ctx.act = feat, p, hid, ops.debug_snapshot(), act
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        need_w = any(ctx.needs_input_grad[1:])
+        need_w = any(ctx.needs_input_grad[2:])
         g = [torch.empty_like(t) for t in ctx.p] if need_w else None
         dfeat = torch.empty_like(ctx.feat) if ctx.needs_input_grad[0] else None
         with ops.debug_scope(ctx.dbg):
-            ops.mlp_bwd(ctx.p, ctx.feat, ctx.hid, dout.contiguous(), dparams=g, dx=dfeat)
-        return (dfeat, *(g if g is not None else [None] * len(ctx.p)))
+            ops.mlp_bwd(ctx.p, ctx.feat, ctx.hid, dout.contiguous(), dparams=g, dx=dfeat, act=ctx.act)
+        return (dfeat, None, *(g if g is not None else [None] * len(ctx.p)))
 
 
 def mlp_apply(mod, belief, state):
     feat = torch.cat([belief, state], dim=1).contiguous()
-    return _MlpFn.apply(feat, *mod.plist())
+    return _MlpFn.apply(feat, getattr(mod, "act", ops.ACT_ELU), *mod.plist())
 
 
 class _ObserveFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, prev_belief, prev_state, actions, embeds, nonterms, eps_prior, eps_post, min_std, *params):
+    def forward(ctx, prev_belief, prev_state, actions, embeds, nonterms, eps_prior, eps_post, min_std, act, *params):
         p = _det(params)
         sv = ops.rssm_observe_fwd(p, prev_belief.contiguous(), prev_state.contiguous(), actions.contiguous(),
                                   nonterms.contiguous(), embeds.contiguous(), eps_prior.contiguous(),
-                                  eps_post.contiguous(), min_std)
+                                  eps_post.contiguous(), min_std, act=act)
         ctx.p, ctx.sv, ctx.min_std, ctx.dbg = p, sv, min_std, ops.debug_snapshot()
         D = sv.D
         outs = (sv.featx[1:, :, :D], sv.prior_state, sv.prior_mean, sv.prior_std, sv.featx[1:, :, D:], sv.post_mean,
@@ -106,7 +106,7 @@ class _ObserveFn(torch.autograd.Function):
             ops.rssm_observe_bwd(ctx.p, sv, g, dfeat=dfeat, dprior_state=dps_.contiguous(), dpm=dpm.contiguous(),
                                  dps=dpsd.contiguous(), dqm=dqm.contiguous(), dqs=dqsd.contiguous(), dembeds=dembeds,
                                  dprev_belief=dpb, dprev_state=dpst, min_std=ctx.min_std)
-        return (dpb, dpst, None, dembeds, None, None, None, None, *g)
+        return (dpb, dpst, None, dembeds, None, None, None, None, None, *g)
 
 
 def observe_apply(mod, prev_belief, prev_state, actions, observations, nonterminals, noise):
@@ -118,7 +118,7 @@ def observe_apply(mod, prev_belief, prev_state, actions, observations, nontermin
     if noise is None:
         noise = (torch.randn(T, B, S, device=dev), torch.randn(T, B, S, device=dev))
     outs = _ObserveFn.apply(prev_belief, prev_state, actions, observations, nonterminals.reshape(T, B), noise[0],
-                            noise[1], float(mod.min_std_dev), *mod.plist())
+                            noise[1], float(mod.min_std_dev), getattr(mod, "act", ops.ACT_ELU), *mod.plist())
     return list(outs)
 
 

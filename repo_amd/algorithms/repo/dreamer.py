@@ -289,6 +289,7 @@ class Dreamer:
             noise=self._draw(2 * T * B * S),
             # the prior head is off the recurrence: evaluated for all steps on the side stream, beside the decoder
             prior_stream=self._side_stream if os.environ.get("REPO_PRIOR_HOIST", "1") == "1" else None,
+            act=self.transition_model.act,
         )
         st["sv"] = sv
         feat = sv.featx[1:].reshape(rows, D + S)
@@ -297,7 +298,7 @@ class Dreamer:
         st["nll_sum"], st["dec_saved"] = Fn.decoder_fwd_nll(pd, feat, frames, 1.0 / grow, head=head)
         # reward head; predicted from the next state, masked by nonterminal (repo.py:58-61)
         pw, _ = self._pg(self.reward_model)
-        r_pred, st["rew_hid"] = ops.mlp_fwd(pw, feat)
+        r_pred, st["rew_hid"] = ops.mlp_fwd(pw, feat, act=self.reward_model.act)
         st["rew_sums"], st["drew"] = ops.scalar_nll(
             r_pred.view(-1), rewards[:-1].reshape(-1).contiguous(), nonterms[:-1].reshape(-1).contiguous(), 1.0 / grow
         )
@@ -312,7 +313,7 @@ class Dreamer:
         wside = self._wgrad_side(st["frames"].shape[0] // sv.featx[1:].shape[0])   # sequences in the batch
         dfeat = torch.empty(rows, feat.shape[1], device=dev)
         pw, gw = self._pg(self.reward_model)
-        ops.mlp_bwd(pw, feat, st["rew_hid"], st["drew"].view(rows, 1), dparams=gw, dx=dfeat)
+        ops.mlp_bwd(pw, feat, st["rew_hid"], st["drew"].view(rows, 1), dparams=gw, dx=dfeat, act=self.reward_model.act)
         pd, gd = self._pg(self.obs_model)
         pr, gr = self._pg(self.transition_model)
         pe, ge = self._pg(self.encoder)
@@ -439,12 +440,16 @@ class Dreamer:
         pv, gv = self._pg(self.value_model)
         pw, _ = self._pg(self.reward_model)
         am = self.actor_model
+        # activations, read at construction: the heads' and the RSSM's are config.dense_activation_function; the actor's is
+        # its own default (the reference's quirk, _build_modules) and the rollout kernels run its trunk with ELU
+        act_r, act_w, act_v, act_a = self.transition_model.act, self.reward_model.act, self.value_model.act, am.act
+        assert act_a == ops.ACT_ELU, "the rollout kernels run the actor trunk with ELU"
         a_consts = (am._min_std, am._init_std, float(am._mean_scale))
         # -- imagine (world model frozen, actor inputs detached)
         sv = ops.rssm_imagine_fwd(
             pr, pa, beliefs.contiguous(), posterior_states.contiguous(), self._noise("img_act", (Hm, N, A)),
             self._noise("img_prior", (Hm, N, S)), self.transition_model.min_std_dev, *a_consts, spare_slot=True,
-            noise=self._draw(Hm * N * (A + S)), horizon=Hm, cond=cond,
+            noise=self._draw(Hm * N * (A + S)), horizon=Hm, cond=cond, act=act_r,
         )
         # every row the heads read: all Hm + 1 slots of the rollout, widened by the condition columns if there is one
         Fw = F_
@@ -460,15 +465,16 @@ class Dreamer:
         # reference computes it all the same): the head runs on the first Hm - 1 steps' rows, forward and backward
         nr_ = (Hm - 1) * N
         r_pred = torch.empty(Hm * N, 1, device=dev)
-        _, r_hid = ops.mlp_fwd(pw, feats[:nr_], out=r_pred[:nr_])
-        v_pred, v_hid = ops.mlp_fwd(pv, feats)
+        _, r_hid = ops.mlp_fwd(pw, feats[:nr_], out=r_pred[:nr_], act=act_w)
+        v_pred, v_hid = ops.mlp_fwd(pv, feats, act=act_v)
         # -- action entropy on the (attached) imagined states (dreamer.py:320-324).  The reference
         #    re-runs the actor on imag[0..Hm-1]; rows of steps 1..Hm-1 are the very inputs the rollout
         #    already pushed through the actor (detaching does not change values), so only the final
         #    state is evaluated here, into the spare step slot of the rollout's saved activations.
         nl = sv.a_hidden.shape[0]
         tail = slice(Hm * N, (Hm + 1) * N)
-        ops.mlp_fwd(pa, x_all[Hm * N:], out=sv.a_raw[tail], hid=[sv.a_hidden[l, tail] for l in range(nl)])
+        ops.mlp_fwd(pa, x_all[Hm * N:], out=sv.a_raw[tail], hid=[sv.a_hidden[l, tail] for l in range(nl)],
+                    act=act_a)
         ops.actor_head_fwd(sv.a_raw[tail], *a_consts, mean=sv.a_mean[tail], std=sv.a_std[tail])
         ent_rows = slice(N, (Hm + 1) * N)  # imagined steps 1..Hm
         mean2, std2 = sv.a_mean[ent_rows], sv.a_std[ent_rows]
@@ -495,17 +501,18 @@ class Dreamer:
         one_chain = os.environ.get("REPO_VALUE_ONE_CHAIN", "1") == "1"
         if one_chain:
             v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), None, 1.0 / ((Hm - 1) * gN))
-            ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=gv, dx=dfeat, dout_w=dv2.view(nv, 1))
+            ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=gv, dx=dfeat, dout_w=dv2.view(nv, 1), act=act_v)
         else:
-            ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat)
-        ops.mlp_bwd(pw, feats[:nr_], r_hid, dr.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_], accumulate_dx=True)
+            ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
+        ops.mlp_bwd(pw, feats[:nr_], r_hid, dr.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_], accumulate_dx=True,
+                    act=act_w)
         # -- the critic's step (one chain: only the optimiser step is left of it), forked onto a side stream: it runs
         #    while the reverse rollout (which fills only ~77 CUs) and the actor backward proceed on the main stream
         side.wait_stream(main)  # after the value head's backward above read the weights
         with torch.cuda.stream(side):
             if not one_chain:
                 v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), None, 1.0 / ((Hm - 1) * gN))
-                ops.mlp_bwd(pv, feats[:nv], [h[:nv] for h in v_hid], dv2.view(nv, 1), dparams=gv, dx=None)
+                ops.mlp_bwd(pv, feats[:nv], [h[:nv] for h in v_hid], dv2.view(nv, 1), dparams=gv, dx=None, act=act_v)
             if self.dp is None:
                 self.value_optimizer.clip_and_step(c.grad_clip_norm)
         # gradient at the actor trunk's output, all (Hm+1)*N rows: rollout path on steps 0..Hm-1
@@ -513,7 +520,7 @@ class Dreamer:
         d_out = torch.zeros((Hm + 1) * N, 2 * A, device=dev)
         draw2 = ops.actor_head_bwd(mean2, std2, dmean=dmean2, dstd=dstd2, min_std=a_consts[0], mean_scale=a_consts[2])
         ops.mlp_bwd(pa, feats, [sv.a_hidden[l, ent_rows] for l in range(nl)], draw2, dparams=None, dx=dfeat,
-                    accumulate_dx=True)
+                    accumulate_dx=True, act=act_a)
         if cond is not None:   # the condition columns take a gradient nobody reads
             dfeat = dfeat[:, :F_].contiguous()
         ops.rssm_imagine_bwd(pr, sv, dfeat, dprior_std=dpstd, min_std=self.transition_model.min_std_dev,
@@ -522,7 +529,8 @@ class Dreamer:
                            out=d_out[ent_rows], accumulate=True)
         # -- ONE actor-trunk backward over every row the actor saw: both gradient paths share the
         #    same forward activations, and the chain is linear in the output gradient
-        ops.mlp_bwd(pa, x_all, [sv.a_hidden[l] for l in range(nl)], d_out, dparams=ga, accumulate_w=False, dx=None)
+        ops.mlp_bwd(pa, x_all, [sv.a_hidden[l] for l in range(nl)], d_out, dparams=ga, accumulate_w=False, dx=None,
+                    act=act_a)
         if self.dp is not None:
             # ONE bucket for both optimisers (their gradients are the halves of self._ac_grad); the critic's
             # backward is joined first, both steps follow the exchange

@@ -12,7 +12,7 @@ class ValueModel(_ScalarHead):
 
 
 class ActorModel(nn.Module):
-    """230 -> hidden^4 -> 2A ELU MLP; mean = mean_scale*tanh(m/mean_scale),
+    """230 -> hidden^4 -> 2A MLP (ELU, or ReLU when given explicitly); mean = mean_scale*tanh(m/mean_scale),
     std = softplus(s + init_std) + min_std; action ~ tanh(Normal(mean, std)).
 
     The reference passes `dense_activation_function` positionally into the `dist` slot
@@ -21,8 +21,7 @@ class ActorModel(nn.Module):
     def __init__(self, belief_size, state_size, hidden_size, action_size, dist="tanh_normal",
                  activation_function="elu", min_std=0.1, init_std=0.0, mean_scale=5):
         super().__init__()
-        if activation_function != "elu":
-            raise NotImplementedError("HIP MLP kernels fuse ELU")
+        self.act = ops.dense_act_id(activation_function, "ActorModel")
         self.fc1 = nn.Linear(belief_size + state_size, hidden_size)
         self.fc2 = nn.Linear(hidden_size, hidden_size)
         self.fc3 = nn.Linear(hidden_size, hidden_size)
@@ -40,7 +39,7 @@ class ActorModel(nn.Module):
     @torch.no_grad()
     def forward(self, belief, state):
         feat = torch.cat([belief, state], dim=1).contiguous()
-        raw, _ = ops.mlp_fwd([t.detach() for t in self.plist()], feat)
+        raw, _ = ops.mlp_fwd([t.detach() for t in self.plist()], feat, act=self.act)
         mean, std, _ = ops.actor_head_fwd(raw, self._min_std, self._init_std, float(self._mean_scale))
         return mean, std
 
@@ -49,7 +48,7 @@ class ActorModel(nn.Module):
         """rsample of the policy (det=False) or SampleDist.mode (det=True): the sample with the
         highest log-probability among `_samples` draws (models/utils.py:149-158)."""
         feat = torch.cat([belief, state], dim=1).contiguous()
-        raw, _ = ops.mlp_fwd([t.detach() for t in self.plist()], feat)
+        raw, _ = ops.mlp_fwd([t.detach() for t in self.plist()], feat, act=self.act)
         if not det:
             if eps is None:
                 eps = torch.randn(raw.shape[0], raw.shape[1] // 2, device=raw.device)

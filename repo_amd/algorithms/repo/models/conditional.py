@@ -95,10 +95,19 @@ def _wide(belief, state, condition):
     return torch.cat([belief, state, condition.float()], dim=1).contiguous()
 
 
+def _elu_only(name, activation_function):
+    """The conditioned dense modules run on the ELU kernels only (the multitask agents are outside the 'relu' support of
+    TransitionModel / RewardModel / ValueModel / ActorModel)."""
+    if activation_function != "elu":
+        raise NotImplementedError(f"{name}: the task-conditioned HIP kernels fuse ELU (dense_activation_function='elu'; "
+                                  "'relu' is supported by the unconditioned modules)")
+
+
 class ConditionalRewardModel(RewardModel):
     """RewardModel on cat([belief, cat([state, condition])]) (models/decoder.py:198-213)."""
 
     def __init__(self, belief_size, state_size, hidden_size, condition_size, activation_function="relu"):
+        _elu_only(type(self).__name__, activation_function)
         super().__init__(belief_size, state_size + condition_size, hidden_size, activation_function)
         self.condition_size = condition_size
 
@@ -110,6 +119,7 @@ class ConditionalRewardModel(RewardModel):
 
 class ConditionalValueModel(ValueModel):
     def __init__(self, belief_size, state_size, hidden_size, condition_size, activation_function="relu"):
+        _elu_only(type(self).__name__, activation_function)
         super().__init__(belief_size, state_size + condition_size, hidden_size, activation_function)
         self.condition_size = condition_size
 
@@ -122,6 +132,7 @@ class ConditionalValueModel(ValueModel):
 class ConditionalActorModel(ActorModel):
     def __init__(self, belief_size, state_size, hidden_size, action_size, condition_size, dist="tanh_normal",
                  activation_function="elu", min_std=0.1, init_std=0.0, mean_scale=5):
+        _elu_only("ConditionalActorModel", activation_function)
         super().__init__(belief_size, state_size + condition_size, hidden_size, action_size, dist, activation_function,
                          min_std, init_std, mean_scale)
         self.condition_size = condition_size
@@ -141,6 +152,7 @@ class ConditionalTransitionModel(TransitionModel):
 
     def __init__(self, belief_size, state_size, action_size, hidden_size, embedding_size, condition_size,
                  activation_function="relu", min_std_dev=0.1):
+        _elu_only("ConditionalTransitionModel", activation_function)
         super().__init__(belief_size, state_size, action_size + condition_size, hidden_size, embedding_size,
                          activation_function, min_std_dev)
         self.condition_size = condition_size

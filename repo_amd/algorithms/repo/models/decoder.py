@@ -73,12 +73,14 @@ def ObservationModel(symbolic, observation_size, belief_size, state_size, embedd
 
 
 class _ScalarHead(nn.Module):
-    """230 -> hidden^3 -> 1 ELU MLP on cat([belief, state])."""
+    """230 -> hidden^3 -> 1 MLP on cat([belief, state]); activation_function "elu" or "relu" (the reference's default
+    argument), `self.act` its REPO_ACT_* id."""
 
     def __init__(self, belief_size, state_size, hidden_size, activation_function="relu"):
         super().__init__()
-        if activation_function != "elu":
-            raise NotImplementedError("HIP MLP kernels fuse ELU (dense_activation_function='elu')")
+        from .... import ops
+
+        self.act = ops.dense_act_id(activation_function, type(self).__name__)
         self.fc1 = nn.Linear(belief_size + state_size, hidden_size)
         self.fc2 = nn.Linear(hidden_size, hidden_size)
         self.fc3 = nn.Linear(hidden_size, hidden_size)

@@ -3,18 +3,31 @@ import torch
 import torch.nn as nn
 
 
+def _rollout_actor_is_elu(policy):
+    """The rollout kernels run the actor trunk with ELU (the reference's agents never hand ActorModel the config's
+    activation: dreamer.py:99-105); an actor built with another one cannot be rolled out by them."""
+    from .... import ops
+
+    if getattr(policy, "act", ops.ACT_ELU) != ops.ACT_ELU:
+        raise NotImplementedError("the HIP rollout kernels run the actor trunk with 'elu'; this ActorModel was built with "
+                                  "another activation_function (supported there: 'elu')")
+
+
 class TransitionModel(nn.Module):
-    """Linear(s+a -> belief) -> ELU -> GRUCell(belief, belief); prior MLP belief -> hidden -> 2s;
+    """Linear(s+a -> belief) -> act -> GRUCell(belief, belief); prior MLP belief -> hidden -> 2s;
     posterior MLP (belief + embedding) -> hidden -> 2s; std = softplus(.) + min_std_dev.
 
     Children are parameter containers (reference constructors, reference state_dict names);
-    `observe` runs the fused HIP scan, `imagine` the HIP rollout."""
+    `observe` runs the fused HIP scan, `imagine` the HIP rollout.  `activation_function` ("elu" or "relu": the agents pass
+    config.dense_activation_function) is the act_fn of every dense layer (reference rssm.py:24); `self.act` is its
+    REPO_ACT_* id, fixed at construction."""
 
     def __init__(self, belief_size, state_size, action_size, hidden_size, embedding_size,
                  activation_function="relu", min_std_dev=0.1):
         super().__init__()
-        if activation_function != "elu":
-            raise NotImplementedError("HIP RSSM kernels fuse ELU (dense_activation_function='elu')")
+        from .... import ops
+
+        self.act = ops.dense_act_id(activation_function, "TransitionModel")
         self.min_std_dev = min_std_dev
         self.belief_size, self.state_size, self.action_size = belief_size, state_size, action_size
         self.hidden_size, self.embedding_size = hidden_size, embedding_size
@@ -64,7 +77,8 @@ class TransitionModel(nn.Module):
         eps = noise[0] if noise is not None else torch.randn(T, B, S, device=dev)
         sv = ops.rssm_observe_fwd([t.detach() for t in self.plist()], prev_belief.contiguous(), prev_state.contiguous(),
                                   actions.contiguous(), nt.contiguous(), torch.zeros(T, B, self.embedding_size, device=dev),
-                                  eps.contiguous(), torch.zeros(T, B, S, device=dev), self.min_std_dev, prior_only=True)
+                                  eps.contiguous(), torch.zeros(T, B, S, device=dev), self.min_std_dev, prior_only=True,
+                                  act=self.act)
         return [sv.featx[1:, :, :D], sv.prior_state, sv.prior_mean, sv.prior_std]
 
     @torch.no_grad()
@@ -74,6 +88,7 @@ class TransitionModel(nn.Module):
         Dreamer.train_actor_critic (repo_rssm_imagine_bwd)."""
         from .... import ops
 
+        _rollout_actor_is_elu(policy)
         N = prev_belief.shape[0]
         dev = prev_belief.device
         A, S = self.action_size, self.state_size
@@ -81,6 +96,7 @@ class TransitionModel(nn.Module):
             noise = (torch.randn(horizon - 1, N, A, device=dev), torch.randn(horizon - 1, N, S, device=dev))
         sv = ops.rssm_imagine_fwd([t.detach() for t in self.plist()], [t.detach() for t in policy.plist()],
                                   prev_belief.contiguous(), prev_state.contiguous(), noise[0], noise[1],
-                                  self.min_std_dev, policy._min_std, policy._init_std, float(policy._mean_scale))
+                                  self.min_std_dev, policy._min_std, policy._init_std, float(policy._mean_scale),
+                                  act=self.act)
         D = self.belief_size
         return [sv.featx[1:, :, :D], sv.featx[1:, :, D:], sv.prior_mean, sv.prior_std]

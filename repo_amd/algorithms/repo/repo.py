@@ -76,10 +76,11 @@ class RePo(Dreamer):
         sv = ops.rssm_observe_fwd(
             pr, *self._zero_state(B), actions[:-1].contiguous(),
             nonterms[:-1].reshape(T, B).contiguous(), embeds.view(T, B, -1), self._noise("obs_prior", (T, B, S)),
-            self._noise("obs_post", (T, B, S)), self.transition_model.min_std_dev, noise=self._draw(2 * T * B * S))
+            self._noise("obs_post", (T, B, S)), self.transition_model.min_std_dev, noise=self._draw(2 * T * B * S),
+            act=self.transition_model.act)
         feat = sv.featx[1:].reshape(rows, D + S)
         pw, gw = self._pg(self.reward_model)
-        r_pred, r_hid = ops.mlp_fwd(pw, feat)
+        r_pred, r_hid = ops.mlp_fwd(pw, feat, act=self.reward_model.act)
         rew_sums, drew = ops.scalar_nll(r_pred.view(-1), rewards[:-1].reshape(-1).contiguous(),
                                         nonterms[:-1].reshape(-1).contiguous(), 1.0 / grow)
         alpha = c.prior_train_steps / (1 + c.prior_train_steps)
@@ -89,7 +90,7 @@ class RePo(Dreamer):
         side.wait_stream(main)
         with torch.cuda.stream(side):
             dfeat = torch.empty(rows, D + S, device=dev)
-            ops.mlp_bwd(pw, feat, r_hid, drew.view(rows, 1), dparams=gw, dx=dfeat)
+            ops.mlp_bwd(pw, feat, r_hid, drew.view(rows, 1), dparams=gw, dx=dfeat, act=self.reward_model.act)
             ev_rew = torch.cuda.Event()
             ev_rew.record(side)   # the reward head's gradients (part of the decoder bucket) are final
             dembeds = torch.empty(rows, c.embedding_size, device=dev)

@@ -46,15 +46,15 @@ class FinetunedRePo(RePo):
         sv = ops.rssm_observe_fwd(
             pr, b0, s0, actions[:-1].contiguous(), nonterms[:-1].reshape(T, B).contiguous(), embeds.view(T, B, -1),
             self._noise("obs_prior", (T, B, S)), self._noise("obs_post", (T, B, S)), self.transition_model.min_std_dev,
-            noise=self._draw(2 * T * B * S))
+            noise=self._draw(2 * T * B * S), act=self.transition_model.act)
         feat = sv.featx[1:].reshape(rows, D + S)
         # reward NLL through the frozen head: only its input gradient
         pw, _ = self._pg(self.reward_model)
-        r_pred, r_hid = ops.mlp_fwd(pw, feat)
+        r_pred, r_hid = ops.mlp_fwd(pw, feat, act=self.reward_model.act)
         rew_sums, drew = ops.scalar_nll(r_pred.view(-1), rewards[:-1].reshape(-1).contiguous(),
                                         nonterms[:-1].reshape(-1).contiguous(), 1.0 / grow)
         dfeat = torch.empty(rows, D + S, device=dev)
-        ops.mlp_bwd(pw, feat, r_hid, drew.view(rows, 1), dparams=None, dx=dfeat)
+        ops.mlp_bwd(pw, feat, r_hid, drew.view(rows, 1), dparams=None, dx=dfeat, act=self.reward_model.act)
         # beta * KL(post || prior), gradient through BOTH arguments: the balanced form with alpha = 1/2, scale 2
         kl_sum, klg = ops.kl_balance(sv.prior_mean, sv.prior_std, sv.post_mean, sv.post_std, 0, 0.5, self.log_beta, 0.0,
                                      2.0 / grow)

@@ -49,6 +49,9 @@ class TIA(Dreamer):
 
     # ------------------------------------------------------------------ construction
     def build_models(self, config, env):
+        if config.dense_activation_function != "elu":
+            raise NotImplementedError("TIA's HIP kernels fuse ELU (dense_activation_function='elu'; 'relu' is supported "
+                                      "by Dreamer, RePo and FinetunedRePo)")
         super().build_models(config, env)
         c, dev = config, self.device
         if env.observation_space.shape[-1] != 64:

@@ -44,6 +44,24 @@ __device__ __forceinline__ float rcp_fast(float x) { return __builtin_amdgcn_rcp
 __device__ __forceinline__ float elu(float x) { return x > 0.f ? x : __expf(x) - 1.f; }
 // derivative of ELU expressed through its OUTPUT h (h = e^x - 1 for x <= 0)
 __device__ __forceinline__ float elu_grad_from_out(float h) { return h > 0.f ? 1.f : h + 1.f; }
+// The dense activation of a kernel (REPO_ACT_*: config.dense_activation_function, the reference's
+// act_fn = getattr(F, activation_function)) is a COMPILE-TIME parameter: one instantiation per activation, no
+// per-element branch in the epilogues.  ACT = REPO_ACT_ELU is exactly elu() / elu_grad_from_out().  Both map
+// 0 -> 0 (zero-padded lanes stay zero) and both derivatives are functions of the saved OUTPUT h.
+template <int ACT>
+__device__ __forceinline__ float act_fn(float x) {
+  if constexpr (ACT == REPO_ACT_RELU) return fmaxf(x, 0.f);
+  else return elu(x);
+}
+template <int ACT>
+__device__ __forceinline__ float act_grad_from_out(float h) {
+  if constexpr (ACT == REPO_ACT_RELU) return h > 0.f ? 1.f : 0.f;
+  else return elu_grad_from_out(h);
+}
+// the repo_gemm epilogues of the host-side GEMM chains
+inline bool act_ok(int act) { return act == REPO_ACT_ELU || act == REPO_ACT_RELU; }
+inline int act_epi(int act) { return act == REPO_ACT_RELU ? REPO_EPI_RELU : REPO_EPI_ELU; }
+inline int act_epi_mul_d(int act) { return act == REPO_ACT_RELU ? REPO_EPI_MUL_DRELU : REPO_EPI_MUL_DELU; }
 // torch F.softplus(beta=1, threshold=20)
 __device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : __logf(1.f + __expf(x)); }
 __device__ __forceinline__ float sigmoidf(float x) { return rcp_fast(1.f + __expf(-x)); }

@@ -1,4 +1,4 @@
-// ELU-MLP heads (reward / value / actor) and the latent imagination rollout.
+// MLP heads (reward / value / actor; ELU or ReLU between the layers) and the latent imagination rollout.
 //
 // Reference: RewardModel / ValueModel / ActorModel forward (models/decoder.py:189-195,
 // models/actor_critic.py:20-26,76-102), TransitionModel.imagine (models/rssm.py:148-184)
@@ -172,11 +172,11 @@ static inline int lin(int64_t rows, int64_t n, int64_t k, const float* x, int64_
                       const float* b, float* y, int64_t ldy, int epi, hipStream_t s) {
   return repo_gemm(0, 1, rows, n, k, x, ldx, w, k, b, 1, y, ldy, epi, nullptr, 0, 0, s);
 }
-// dx = (dy @ W) [* elu'(aux)]
+// dx = (dy @ W) [* act'(aux)]
 static inline int lin_bwd_data(int64_t rows, int64_t n, int64_t k, const float* dy, int64_t lddy, const float* w,
                                float* dx, int64_t lddx, const float* aux, int64_t ldaux, int accumulate,
-                               hipStream_t s) {
-  return repo_gemm(0, 0, rows, k, n, dy, lddy, w, k, nullptr, 1, dx, lddx, aux ? REPO_EPI_MUL_DELU : REPO_EPI_NONE,
+                               hipStream_t s, int act) {
+  return repo_gemm(0, 0, rows, k, n, dy, lddy, w, k, nullptr, 1, dx, lddx, aux ? act_epi_mul_d(act) : REPO_EPI_NONE,
                    aux, ldaux, accumulate, s);
 }
 
@@ -201,13 +201,13 @@ int imagine_fused_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, i
                       NoiseSrc eps_act, NoiseSrc eps_prior, float min_std, float a_min_std, float a_init_std, float a_mean_scale,
                       float* featx, float* prior_mean, float* prior_std, float* a_hidden, int64_t a_layer_rows,
                       float* a_raw, float* a_mean, float* a_std, float* xsa, float* e, float* gates, float* hp, void* ws,
-                      hipStream_t stream);
+                      hipStream_t stream, int act);
 int imagine_fused_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S, const float* const* rp,
                       int64_t C, NoiseSrc eps_act, NoiseSrc eps_prior, float min_std, float a_min_std,
                       float a_mean_scale, const float* featx, const float* prior_std, const float* a_mean,
                       const float* a_std, const float* xsa, const float* e, const float* gates, const float* hp,
                       const float* dfeat, const float* dprior_mean, const float* dprior_std, float* d_araw,
-                      float* dfeat0, void* ws, hipStream_t stream);
+                      float* dfeat0, void* ws, hipStream_t stream, int act);
 
 // the same rollout on 32-row tiles and the bf16 matrix pipe (imagine32.hip)
 bool imagine32_ok(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S, int n_actor_layers, int64_t C);
@@ -217,24 +217,24 @@ int imagine32_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64
                   NoiseSrc eps_act, NoiseSrc eps_prior, float min_std, float a_min_std, float a_init_std,
                   float a_mean_scale, float* featx, float* prior_mean, float* prior_std, float* a_hidden,
                   int64_t a_layer_rows, float* a_raw, float* a_mean, float* a_std, float* xsa, float* e, float* gates,
-                  float* hp, void* ws, hipStream_t stream);
+                  float* hp, void* ws, hipStream_t stream, int act);
 
 size_t imagine32_bwd_ws_bytes(int64_t A, int64_t D, int64_t Hd, int64_t S);
 int imagine32_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S, const float* const* rp, int64_t C,
                   NoiseSrc eps_act, NoiseSrc eps_prior, float min_std, float a_min_std, float a_mean_scale,
                   const float* featx, const float* prior_std, const float* a_mean, const float* a_std, const float* xsa,
                   const float* e, const float* gates, const float* hp, const float* dfeat, const float* dprior_mean,
-                  const float* dprior_std, float* d_araw, float* dfeat0, void* ws, hipStream_t stream);
+                  const float* dprior_std, float* d_araw, float* dfeat0, void* ws, hipStream_t stream, int act);
 
 // fused dense heads (mlp16.hip)
 bool mlp_fused_ok(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers);
 size_t mlp_fused_ws_floats(int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers);
 int mlp_fused_fwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int L, const float* x, int64_t ldx,
                   const float* const* params, float* const* hidden_out, float* out, int64_t ldo, void* ws,
-                  hipStream_t stream);
+                  hipStream_t stream, int act);
 int mlp_fused_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int L, const float* const* params,
                   const float* const* hidden_acts, const float* dout, int64_t lddout, float* const* dsave, float* dx,
-                  int64_t lddx, int accumulate_dx, void* ws, hipStream_t stream, const float* dout_w = nullptr,
+                  int64_t lddx, int accumulate_dx, void* ws, hipStream_t stream, int act, const float* dout_w = nullptr,
                   int64_t rows_w = 0);
 
 }  // namespace repo
@@ -251,14 +251,14 @@ static bool mlp_quads_aligned(int n_layers, const float* const* params, const fl
 
 static int mlp_fwd_layers(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers, const float* x,
                           int64_t ldx, const float* const* params, float* const* hidden_out, float* out, int64_t ldo,
-                          hipStream_t stream) {
+                          hipStream_t stream, int act) {
   const float* cur = x;
   int64_t ldc = ldx, kc = in_dim;
   for (int l = 0; l < n_layers; ++l) {
     const bool last = l == n_layers - 1;
     float* y = last ? out : hidden_out[l];
     const int64_t n = last ? out_dim : hidden, ldy = last ? ldo : hidden;
-    REPO_RC(lin(rows, n, kc, cur, ldc, params[2 * l], params[2 * l + 1], y, ldy, last ? REPO_EPI_NONE : REPO_EPI_ELU,
+    REPO_RC(lin(rows, n, kc, cur, ldc, params[2 * l], params[2 * l + 1], y, ldy, last ? REPO_EPI_NONE : act_epi(act),
                 stream));
     cur = y;
     ldc = ldy;
@@ -274,10 +274,11 @@ extern "C" size_t repo_mlp_fwd_workspace_bytes(int64_t rows, int64_t in_dim, int
              : 0;
 }
 
-extern "C" int repo_mlp_fwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers,
+extern "C" int repo_mlp_fwd_act(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers,
                             const float* x, int64_t ldx, const float* const* params, float* const* hidden_out,
-                            float* out, int64_t ldo, void* ws, size_t ws_bytes, hipStream_t stream) {
+                            float* out, int64_t ldo, void* ws, size_t ws_bytes, hipStream_t stream, int act) {
   REPO_ARCH_GUARD();
+  REPO_REQUIRE(act_ok(act), REPO_E_BADARG);
   REPO_REQUIRE(rows >= 0 && in_dim > 0 && hidden > 0 && out_dim > 0 && n_layers >= 1, REPO_E_SHAPE);
   if (rows == 0) return REPO_OK;
   REPO_REQUIRE(x && params && out && (n_layers == 1 || hidden_out), REPO_E_BADARG);
@@ -286,9 +287,9 @@ extern "C" int repo_mlp_fwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_
       mlp_quads_aligned(n_layers, params, hidden_out)) {
     REPO_REQUIRE(ws && ws_bytes >= repo_mlp_fwd_workspace_bytes(rows, in_dim, hidden, out_dim, n_layers),
                  REPO_E_WS_TOO_SMALL);
-    return mlp_fused_fwd(rows, in_dim, hidden, out_dim, n_layers, x, ldx, params, hidden_out, out, ldo, ws, stream);
+    return mlp_fused_fwd(rows, in_dim, hidden, out_dim, n_layers, x, ldx, params, hidden_out, out, ldo, ws, stream, act);
   }
-  return mlp_fwd_layers(rows, in_dim, hidden, out_dim, n_layers, x, ldx, params, hidden_out, out, ldo, stream);
+  return mlp_fwd_layers(rows, in_dim, hidden, out_dim, n_layers, x, ldx, params, hidden_out, out, ldo, stream, act);
 }
 
 // workspace: [pre-activation gradients: (n_layers - 1) x rows x hidden | weight-gradient slab | packs]
@@ -325,12 +326,14 @@ extern "C" size_t repo_mlp_bwd_workspace_bytes(int64_t rows, int64_t in_dim, int
          (fused ? mlp_fused_ws_floats(in_dim, hidden, out_dim, n_layers) * sizeof(float) : 0) + 512;
 }
 
-extern "C" int repo_mlp_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers,
+extern "C" int repo_mlp_bwd_act(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers,
                             const float* x, int64_t ldx, const float* const* params,
                             const float* const* hidden_acts, const float* dout, int64_t lddout,
                             float* const* dparams, int accumulate_w, float* dx, int64_t lddx, int accumulate_dx,
-                            const float* dout_w, int64_t rows_w, void* ws, size_t ws_bytes, hipStream_t stream) {
+                            const float* dout_w, int64_t rows_w, void* ws, size_t ws_bytes, hipStream_t stream,
+                            int act) {
   REPO_ARCH_GUARD();
+  REPO_REQUIRE(act_ok(act), REPO_E_BADARG);
   REPO_REQUIRE(rows > 0 && in_dim > 0 && hidden > 0 && out_dim > 0 && n_layers >= 1, REPO_E_SHAPE);
   REPO_REQUIRE(x && params && dout && (n_layers == 1 || hidden_acts), REPO_E_BADARG);
   REPO_REQUIRE(ws && ws_bytes >= repo_mlp_bwd_workspace_bytes(rows, in_dim, hidden, out_dim, n_layers),
@@ -340,10 +343,10 @@ extern "C" int repo_mlp_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_
     if (!(mlp_fused_ok(rows, in_dim, hidden, out_dim, n_layers) && mlp_quads_aligned(n_layers, params, hidden_acts) &&
           ((uintptr_t)ws & 15) == 0)) {
       // no fused chain for this shape: the two passes the one-chain form replaces
-      REPO_RC(repo_mlp_bwd(rows, in_dim, hidden, out_dim, n_layers, x, ldx, params, hidden_acts, dout, lddout, nullptr, 0,
-                           dx, lddx, accumulate_dx, nullptr, 0, ws, ws_bytes, stream));
-      return repo_mlp_bwd(rows_w, in_dim, hidden, out_dim, n_layers, x, ldx, params, hidden_acts, dout_w, 1, dparams,
-                          accumulate_w, nullptr, 0, 0, nullptr, 0, ws, ws_bytes, stream);
+      REPO_RC(repo_mlp_bwd_act(rows, in_dim, hidden, out_dim, n_layers, x, ldx, params, hidden_acts, dout, lddout, nullptr,
+                               0, dx, lddx, accumulate_dx, nullptr, 0, ws, ws_bytes, stream, act));
+      return repo_mlp_bwd_act(rows_w, in_dim, hidden, out_dim, n_layers, x, ldx, params, hidden_acts, dout_w, 1, dparams,
+                              accumulate_w, nullptr, 0, 0, nullptr, 0, ws, ws_bytes, stream, act);
     }
   }
   const bool shape_ok = mlp_fused_ok(rows, in_dim, hidden, out_dim, n_layers);
@@ -358,8 +361,8 @@ extern "C" int repo_mlp_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_
     float* dsave[8];
     for (int l = 0; l < n_layers - 1; ++l) dsave[l] = d0 + (size_t)l * rows * hidden;
     REPO_RC(mlp_fused_bwd(rows, in_dim, hidden, out_dim, n_layers, params, hidden_acts, dout, lddout,
-                          dparams ? dsave : nullptr, dx, lddx, accumulate_dx, (void*)(sl + slab_bytes), stream, dout_w,
-                          rows_w));
+                          dparams ? dsave : nullptr, dx, lddx, accumulate_dx, (void*)(sl + slab_bytes), stream, act,
+                          dout_w, rows_w));
     if (!dparams) return REPO_OK;
     WgradDesc jobs[kMaxWgradGroup];
     const int nj = mlp_wgrad_jobs(jobs, dout_w ? rows_w : rows, in_dim, hidden, out_dim, n_layers, x, ldx, hidden_acts,
@@ -379,11 +382,11 @@ extern "C" int repo_mlp_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_
                               slab, slab_bytes, stream));
     if (l > 0) {
       float* dn = (dcur == d0) ? d1 : d0;
-      REPO_RC(lin_bwd_data(rows, n, k, dcur, lddc, params[2 * l], dn, hidden, hidden_acts[l - 1], hidden, 0, stream));
+      REPO_RC(lin_bwd_data(rows, n, k, dcur, lddc, params[2 * l], dn, hidden, hidden_acts[l - 1], hidden, 0, stream, act));
       dcur = dn;
       lddc = hidden;
     } else if (dx) {
-      REPO_RC(lin_bwd_data(rows, n, k, dcur, lddc, params[0], dx, lddx, nullptr, 0, accumulate_dx, stream));
+      REPO_RC(lin_bwd_data(rows, n, k, dcur, lddc, params[0], dx, lddx, nullptr, 0, accumulate_dx, stream, act));
     }
   }
   return REPO_OK;
@@ -441,7 +444,7 @@ extern "C" size_t repo_rssm_imagine_fwd_workspace_bytes(int64_t Hm, int64_t N, i
   return unfused > fused ? unfused : fused;
 }
 
-extern "C" int repo_rssm_imagine_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S,
+extern "C" int repo_rssm_imagine_fwd_act(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S,
                                      int n_actor_layers, const float* const* rssm_params,
                                      const float* const* actor_params, const float* belief0, const float* state0,
                                      const float* cond, int64_t C,
@@ -450,8 +453,9 @@ extern "C" int repo_rssm_imagine_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D
                                      float a_init_std, float a_mean_scale, float* featx, float* prior_mean,
                                      float* prior_std, float* a_hidden, int64_t a_layer_rows, float* a_raw,
                                      float* a_mean, float* a_std, float* xsa, float* e, float* gates, float* hp,
-                                     void* ws, size_t ws_bytes, hipStream_t stream) {
+                                     void* ws, size_t ws_bytes, hipStream_t stream, int act) {
   REPO_ARCH_GUARD();
+  REPO_REQUIRE(act_ok(act), REPO_E_BADARG);
   REPO_REQUIRE(img_dims_ok(Hm, N, A, D, Hd, S) && n_actor_layers >= 2 && n_actor_layers <= 8, REPO_E_SHAPE);
   REPO_REQUIRE(a_layer_rows >= Hm * N, REPO_E_SHAPE);
   REPO_REQUIRE(rssm_params && actor_params && belief0 && state0 && !eps_act == !eps_prior && featx && prior_mean &&
@@ -468,12 +472,12 @@ extern "C" int repo_rssm_imagine_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D
                          NoiseSrc{eps_act, noise_seed, noise_offset},
                          NoiseSrc{eps_prior, noise_seed, noise_offset + (uint64_t)(Hm * N * A)}, min_std, a_min_std,
                          a_init_std, a_mean_scale, featx, prior_mean, prior_std, a_hidden, a_layer_rows, a_raw, a_mean,
-                         a_std, xsa, e, gates, hp, ws, stream);
+                         a_std, xsa, e, gates, hp, ws, stream, act);
   if (imagine_fused_ok(Hm, N, A, D, Hd, S, n_actor_layers, C))
     return imagine_fused_fwd(Hm, N, A, D, Hd, S, rssm_params, actor_params, belief0, state0, cond, C,
                              NoiseSrc{eps_act, noise_seed, noise_offset},
                              NoiseSrc{eps_prior, noise_seed, noise_offset + (uint64_t)(Hm * N * A)}, min_std, a_min_std, a_init_std, a_mean_scale, featx, prior_mean, prior_std, a_hidden,
-                             a_layer_rows, a_raw, a_mean, a_std, xsa, e, gates, hp, ws, stream);
+                             a_layer_rows, a_raw, a_mean, a_std, xsa, e, gates, hp, ws, stream, act);
   const int64_t F = D + S, X = S + A + C, Fw = F + C, rowsAll = Hm * N;   // X, Fw: the conditioned rows' widths
   const float* const* P = rssm_params;
   float* gi = (float*)ws;
@@ -512,18 +516,20 @@ extern "C" int repo_rssm_imagine_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D
       REPO_CHECK_LAUNCH();
       ain = wide;
     }
-    REPO_RC(mlp_fwd_layers(N, Fw, Hd, 2 * A, n_actor_layers, ain, Fw, actor_params, hid, a_raw + r0 * 2 * A, 2 * A, stream));
+    // (the actor trunk is ELU whatever `act` says: the reference never passes it the config's activation)
+    REPO_RC(mlp_fwd_layers(N, Fw, Hd, 2 * A, n_actor_layers, ain, Fw, actor_params, hid, a_raw + r0 * 2 * A, 2 * A, stream,
+                           REPO_ACT_ELU));
     REPO_RC(actor_head_fwd_ld(N, A, S, a_raw + r0 * 2 * A, eps_act + r0 * A, ft + D, F, a_min_std, a_init_std,
                               a_mean_scale, a_mean + r0 * A, a_std + r0 * A, xsa + r0 * X, X, stream));
     // belief update
-    REPO_RC(lin(N, D, X, xsa + r0 * X, X, P[0], P[1], e + r0 * D, D, REPO_EPI_ELU, stream));
+    REPO_RC(lin(N, D, X, xsa + r0 * X, X, P[0], P[1], e + r0 * D, D, act_epi(act), stream));
     REPO_RC(lin(N, 3 * D, D, e + r0 * D, D, P[2], P[4], gi, 3 * D, REPO_EPI_NONE, stream));
     REPO_RC(lin(N, 3 * D, D, ft, F, P[3], P[5], gh, 3 * D, REPO_EPI_NONE, stream));
     hipLaunchKernelGGL(gru_fwd_kernel, dim3(ew_blocks(N * D)), dim3(256), 0, stream, (int)N, (int)D, gi, gh, ft,
                        (int)F, fn, (int)F, gates + r0 * 4 * D);
     REPO_CHECK_LAUNCH();
     // prior head
-    REPO_RC(lin(N, Hd, D, fn, F, P[6], P[7], hp + r0 * Hd, Hd, REPO_EPI_ELU, stream));
+    REPO_RC(lin(N, Hd, D, fn, F, P[6], P[7], hp + r0 * Hd, Hd, act_epi(act), stream));
     REPO_RC(lin(N, 2 * S, Hd, hp + r0 * Hd, Hd, P[8], P[9], pout, 2 * S, REPO_EPI_NONE, stream));
     hipLaunchKernelGGL(gauss_fwd_kernel, dim3(ew_blocks(N * S)), dim3(256), 0, stream, (int)N, (int)S, pout,
                        eps_prior + r0 * S, min_std, prior_mean + r0 * S, prior_std + r0 * S, fn + D, (int)F);
@@ -541,15 +547,17 @@ extern "C" size_t repo_rssm_imagine_bwd_workspace_bytes(int64_t Hm, int64_t N, i
   return unfused > fused ? unfused : fused;
 }
 
-extern "C" int repo_rssm_imagine_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t C,
+extern "C" int repo_rssm_imagine_bwd_act(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t C,
                                      const float* const* rssm_params, const float* eps_act, const float* eps_prior,
                                      uint64_t noise_seed, uint64_t noise_offset, float min_std, float a_min_std,
                                      float a_mean_scale, const float* featx,
                                      const float* prior_std, const float* a_mean, const float* a_std,
                                      const float* xsa, const float* e, const float* gates, const float* hp,
                                      const float* dfeat, const float* dprior_mean, const float* dprior_std,
-                                     float* d_araw, float* dfeat0, void* ws, size_t ws_bytes, hipStream_t stream) {
+                                     float* d_araw, float* dfeat0, void* ws, size_t ws_bytes, hipStream_t stream,
+                                     int act) {
   REPO_ARCH_GUARD();
+  REPO_REQUIRE(act_ok(act), REPO_E_BADARG);
   REPO_REQUIRE(img_dims_ok(Hm, N, A, D, Hd, S), REPO_E_SHAPE);
   REPO_REQUIRE(rssm_params && !eps_act == !eps_prior && featx && prior_std && a_mean && a_std && xsa && e && gates &&
                    hp && dfeat && d_araw,
@@ -560,12 +568,12 @@ extern "C" int repo_rssm_imagine_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D
     return imagine32_bwd(Hm, N, A, D, Hd, S, rssm_params, C, NoiseSrc{eps_act, noise_seed, noise_offset},
                          NoiseSrc{eps_prior, noise_seed, noise_offset + (uint64_t)(Hm * N * A)}, min_std, a_min_std,
                          a_mean_scale, featx, prior_std, a_mean, a_std, xsa, e, gates, hp, dfeat, dprior_mean,
-                         dprior_std, d_araw, dfeat0, ws, stream);
+                         dprior_std, d_araw, dfeat0, ws, stream, act);
   if (imagine_fused_ok(Hm, N, A, D, Hd, S, 5, C))
     return imagine_fused_bwd(Hm, N, A, D, Hd, S, rssm_params, C, NoiseSrc{eps_act, noise_seed, noise_offset},
                              NoiseSrc{eps_prior, noise_seed, noise_offset + (uint64_t)(Hm * N * A)}, min_std, a_min_std, a_mean_scale,
                              featx, prior_std, a_mean, a_std, xsa, e, gates, hp, dfeat, dprior_mean, dprior_std,
-                             d_araw, dfeat0, ws, stream);
+                             d_araw, dfeat0, ws, stream, act);
   const int64_t F = D + S, X = S + A + C;   // xsa rows = [state | action | cond]; the cond columns' gradient is unused
   const float* const* P = rssm_params;
   float* w = (float*)ws;
@@ -600,16 +608,16 @@ extern "C" int repo_rssm_imagine_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D
                        dprior_std ? dprior_std + r0 * S : (const float*)nullptr, prior_std + r0 * S,
                        eps_prior + r0 * S, min_std, dpout);
     REPO_CHECK_LAUNCH();
-    REPO_RC(lin_bwd_data(N, 2 * S, Hd, dpout, 2 * S, P[8], dhp, Hd, hp + r0 * Hd, Hd, 0, stream));
+    REPO_RC(lin_bwd_data(N, 2 * S, Hd, dpout, 2 * S, P[8], dhp, Hd, hp + r0 * Hd, Hd, 0, stream, act));
     // dbel = g[:, :D] + dhp @ W_bp   (accumulate into g's belief columns in place)
-    REPO_RC(lin_bwd_data(N, Hd, D, dhp, Hd, P[6], g, F, nullptr, 0, 1, stream));
+    REPO_RC(lin_bwd_data(N, Hd, D, dhp, Hd, P[6], g, F, nullptr, 0, 1, stream, act));
     // GRU backward: writes carry[:, :D] = dbel * z
     hipLaunchKernelGGL(gru_bwd_kernel, dim3(ew_blocks(N * D)), dim3(256), 0, stream, (int)N, (int)D, g, (int)F,
                        gates + r0 * 4 * D, ft, (int)F, dgi, dgh, carry, (int)F);
     REPO_CHECK_LAUNCH();
-    REPO_RC(lin_bwd_data(N, 3 * D, D, dgh, 3 * D, P[3], carry, F, nullptr, 0, 1, stream));
-    REPO_RC(lin_bwd_data(N, 3 * D, D, dgi, 3 * D, P[2], de, D, e + r0 * D, D, 0, stream));
-    REPO_RC(lin_bwd_data(N, D, X, de, D, P[0], dxsa, X, nullptr, 0, 0, stream));
+    REPO_RC(lin_bwd_data(N, 3 * D, D, dgh, 3 * D, P[3], carry, F, nullptr, 0, 1, stream, act));
+    REPO_RC(lin_bwd_data(N, 3 * D, D, dgi, 3 * D, P[2], de, D, e + r0 * D, D, 0, stream, act));
+    REPO_RC(lin_bwd_data(N, D, X, de, D, P[0], dxsa, X, nullptr, 0, 0, stream, act));
     // carry[:, D:] = d state_t ; d action -> actor head
     hipLaunchKernelGGL(add_cols_kernel, dim3(ew_blocks(N * S)), dim3(256), 0, stream, (int)N, (int)S, dxsa, (int)X,
                        (const float*)nullptr, 0, carry + D, (int)F);
@@ -625,4 +633,50 @@ extern "C" int repo_rssm_imagine_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D
     REPO_CHECK_LAUNCH();
   }
   return REPO_OK;
+}
+
+// ---- the pre-v9 entry points: the ELU instantiations
+extern "C" int repo_mlp_fwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers,
+                            const float* x, int64_t ldx, const float* const* params, float* const* hidden_out,
+                            float* out, int64_t ldo, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return repo_mlp_fwd_act(rows, in_dim, hidden, out_dim, n_layers, x, ldx, params, hidden_out, out, ldo, ws, ws_bytes,
+                          stream, REPO_ACT_ELU);
+}
+
+extern "C" int repo_mlp_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers,
+                            const float* x, int64_t ldx, const float* const* params,
+                            const float* const* hidden_acts, const float* dout, int64_t lddout,
+                            float* const* dparams, int accumulate_w, float* dx, int64_t lddx, int accumulate_dx,
+                            const float* dout_w, int64_t rows_w, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return repo_mlp_bwd_act(rows, in_dim, hidden, out_dim, n_layers, x, ldx, params, hidden_acts, dout, lddout, dparams,
+                          accumulate_w, dx, lddx, accumulate_dx, dout_w, rows_w, ws, ws_bytes, stream, REPO_ACT_ELU);
+}
+
+extern "C" int repo_rssm_imagine_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S,
+                                     int n_actor_layers, const float* const* rssm_params,
+                                     const float* const* actor_params, const float* belief0, const float* state0,
+                                     const float* cond, int64_t C,
+                                     const float* eps_act, const float* eps_prior, uint64_t noise_seed,
+                                     uint64_t noise_offset, float min_std, float a_min_std,
+                                     float a_init_std, float a_mean_scale, float* featx, float* prior_mean,
+                                     float* prior_std, float* a_hidden, int64_t a_layer_rows, float* a_raw,
+                                     float* a_mean, float* a_std, float* xsa, float* e, float* gates, float* hp,
+                                     void* ws, size_t ws_bytes, hipStream_t stream) {
+  return repo_rssm_imagine_fwd_act(Hm, N, A, D, Hd, S, n_actor_layers, rssm_params, actor_params, belief0, state0, cond, C,
+                                   eps_act, eps_prior, noise_seed, noise_offset, min_std, a_min_std, a_init_std,
+                                   a_mean_scale, featx, prior_mean, prior_std, a_hidden, a_layer_rows, a_raw, a_mean,
+                                   a_std, xsa, e, gates, hp, ws, ws_bytes, stream, REPO_ACT_ELU);
+}
+
+extern "C" int repo_rssm_imagine_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t C,
+                                     const float* const* rssm_params, const float* eps_act, const float* eps_prior,
+                                     uint64_t noise_seed, uint64_t noise_offset, float min_std, float a_min_std,
+                                     float a_mean_scale, const float* featx,
+                                     const float* prior_std, const float* a_mean, const float* a_std,
+                                     const float* xsa, const float* e, const float* gates, const float* hp,
+                                     const float* dfeat, const float* dprior_mean, const float* dprior_std,
+                                     float* d_araw, float* dfeat0, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return repo_rssm_imagine_bwd_act(Hm, N, A, D, Hd, S, C, rssm_params, eps_act, eps_prior, noise_seed, noise_offset,
+                                   min_std, a_min_std, a_mean_scale, featx, prior_std, a_mean, a_std, xsa, e, gates, hp,
+                                   dfeat, dprior_mean, dprior_std, d_araw, dfeat0, ws, ws_bytes, stream, REPO_ACT_ELU);
 }

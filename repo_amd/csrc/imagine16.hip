@@ -55,7 +55,7 @@ struct ImgFwdArgs {
 };
 
 // BF / BW / BX / BS: 16-k blocks of F = D + S, of D and Hd, of X = S + A, of 2 S
-template <int BF, int BW, int BX, int BS>
+template <int BF, int BW, int BX, int BS, int ACT>
 __global__ __launch_bounds__(512) void imagine_fwd_kernel(ImgFwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int Hm = p.d.Hm, N = p.d.N, A = p.d.A, D = p.d.D, Hd = p.d.Hd, S = p.d.S, C = p.d.C;
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(512) void imagine_fwd_kernel(ImgFwdArgs p) {
       if (row < nr) p.xsa[(rb + row) * XL + k] = v;
     }
     __syncthreads();
-    // ---------------- e = elu(W_sa x + b); meanwhile the GRU's first stream and the prior head's are opened
+    // ---------------- e = act(W_sa x + b); meanwhile the GRU's first stream and the prior head's are opened
     const int gtiles = (D + 15) >> 4;
     const int gcol0 = min(wave * 16 + (lane & 15), D - 1), gcol1 = min((wave + kW) * 16 + (lane & 15), D - 1);
     const bool g0 = wave < gtiles, g1 = wave + kW < gtiles;
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(512) void imagine_fwd_kernel(ImgFwdArgs p) {
       const f32x4v bv = ldbias(rw, p.Bsa, n0);
       f32x4v v;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = elu(acc[r] + bv[r]);
+      for (int r = 0; r < 4; ++r) v[r] = act_fn<ACT>(acc[r] + bv[r]);
       stq(HA, n0, lm, v);
       if (lst) bstq(q_e, 4u * (lrow * D + n0), 4u * tN * D, v, 4);
     });
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(512) void imagine_fwd_kernel(ImgFwdArgs p) {
       const f32x4v bv = ldbias(rw, p.Bbp, n0);
       f32x4v v;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = elu(acc[r] + bv[r]);
+      for (int r = 0; r < 4; ++r) v[r] = act_fn<ACT>(acc[r] + bv[r]);
       stq(HB, n0, lm, v);
       if (lst) bstq(q_hp, 4u * (lrow * Hd + n0), 4u * tN * Hd, v, 4);
     });
@@ -278,7 +278,7 @@ struct ImgBwdArgs {
   float *d_araw, *dfeat0;
 };
 
-template <int BF, int BW, int BX, int BS>
+template <int BF, int BW, int BX, int BS, int ACT>
 __global__ __launch_bounds__(512) void imagine_bwd_kernel(ImgBwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int Hm = p.d.Hm, N = p.d.N, A = p.d.A, D = p.d.D, Hd = p.d.Hd, S = p.d.S;
@@ -337,14 +337,14 @@ __global__ __launch_bounds__(512) void imagine_bwd_kernel(ImgBwdArgs p) {
       SM[ai(S + s, row)] = gr;
     }
     __syncthreads();
-    // ---- X1 = (d out @ W_sp) * elu'(hp)
+    // ---- X1 = (d out @ W_sp) * act'(hp)
     dense_open<BW>(w1, rw, p.Wbp, D, wave, lane);
     dense_run<BS>(SM, w0, rw, Hd, wave, lane, [=](bool ok, int n0, const f32x4v& acc) {
       if (!ok) return;
       const f32x4v h = bldq(q_hp, 4u * (lrow * Hd + n0), 4u * tN * Hd);
       f32x4v v;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = acc[r] * elu_grad_from_out(h[r]);
+      for (int r = 0; r < 4; ++r) v[r] = acc[r] * act_grad_from_out<ACT>(h[r]);
       stq(X1, n0, lm, v);
     });
     __syncthreads();
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(512) void imagine_bwd_kernel(ImgBwdArgs p) {
           const f32x4v ev = bldq(q_e, 4u * (lrow * D + n0), 4u * tN * D);
           f32x4v v;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = ae[r] * elu_grad_from_out(ev[r]);
+          for (int r = 0; r < 4; ++r) v[r] = ae[r] * act_grad_from_out<ACT>(ev[r]);
           stq(X4, n0, lm, v);  // d pre-activation of fc_embed_state_action
         }
       }
@@ -481,7 +481,7 @@ int imagine_fused_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, i
                       NoiseSrc eps_act, NoiseSrc eps_prior, float min_std, float a_min_std, float a_init_std,
                       float a_mean_scale, float* featx, float* prior_mean, float* prior_std, float* a_hidden,
                       int64_t a_layer_rows, float* a_raw, float* a_mean, float* a_std, float* xsa, float* e,
-                      float* gates, float* hp, void* ws, hipStream_t stream) {
+                      float* gates, float* hp, void* ws, hipStream_t stream, int act) {
   const int F = (int)(D + S + C), X = (int)(S + A + C);  // K of the two widened layers (C = 0: the reference's)
   float* w = (float*)ws;
   ImgFwdArgs a;
@@ -523,10 +523,10 @@ int imagine_fused_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, i
   a.a_layer_rows = (size_t)a_layer_rows;
   const int W = (int)(D > Hd ? D : Hd), SMr = (int)(2 * A > 2 * S ? 2 * A : 2 * S);
   const size_t lds_b = (size_t)(2 * pad16(F) + 2 * pad16(W) + pad16(X) + pad16(SMr)) * kR * sizeof(float);
-  hipError_t he = hipFuncSetAttribute((const void*)imagine_fwd_kernel<kBF, kBW, kBX, kBS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds_b);
+  auto kern = act == REPO_ACT_RELU ? imagine_fwd_kernel<kBF, kBW, kBX, kBS, REPO_ACT_RELU> : imagine_fwd_kernel<kBF, kBW, kBX, kBS, REPO_ACT_ELU>;
+  hipError_t he = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
   if (he != hipSuccess) return (int)he;
-  hipLaunchKernelGGL((imagine_fwd_kernel<kBF, kBW, kBX, kBS>), dim3((unsigned)((N + kR - 1) / kR)), dim3(512), lds_b, stream, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((N + kR - 1) / kR)), dim3(512), lds_b, stream, a);
   he = hipGetLastError();
   return he == hipSuccess ? REPO_OK : (int)he;
 }
@@ -536,7 +536,7 @@ int imagine_fused_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, i
                       float a_mean_scale, const float* featx, const float* prior_std, const float* a_mean,
                       const float* a_std, const float* xsa, const float* e, const float* gates, const float* hp,
                       const float* dfeat, const float* dprior_mean, const float* dprior_std, float* d_araw,
-                      float* dfeat0, void* ws, hipStream_t stream) {
+                      float* dfeat0, void* ws, hipStream_t stream, int act) {
   const int X = (int)(S + A);
   float* w = (float*)ws;
   ImgBwdArgs a;
@@ -569,10 +569,10 @@ int imagine_fused_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, i
   a.d_araw = d_araw; a.dfeat0 = dfeat0;
   const int W = (int)(D > Hd ? D : Hd), SMr = (int)(2 * S > X ? 2 * S : X);
   const size_t lds_b = (size_t)(pad16((int)D) + pad16((int)S) + pad16(SMr) + 4 * pad16(W)) * kR * sizeof(float);
-  hipError_t he = hipFuncSetAttribute((const void*)imagine_bwd_kernel<kBF, kBW, kBX, kBS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds_b);
+  auto kern = act == REPO_ACT_RELU ? imagine_bwd_kernel<kBF, kBW, kBX, kBS, REPO_ACT_RELU> : imagine_bwd_kernel<kBF, kBW, kBX, kBS, REPO_ACT_ELU>;
+  hipError_t he = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
   if (he != hipSuccess) return (int)he;
-  hipLaunchKernelGGL((imagine_bwd_kernel<kBF, kBW, kBX, kBS>), dim3((unsigned)((N + kR - 1) / kR)), dim3(512), lds_b, stream, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((N + kR - 1) / kR)), dim3(512), lds_b, stream, a);
   he = hipGetLastError();
   return he == hipSuccess ? REPO_OK : (int)he;
 }

@@ -48,7 +48,7 @@ __device__ __forceinline__ void dopen32(Win32& w, __amdgpu_buffer_rsrc_t rw, uns
 }
 
 // BF / BW / BX: 16-k blocks of F = D + S (+ C), of D and Hd, of X = S + A (+ C)
-template <int BF, int BW, int BX>
+template <int BF, int BW, int BX, int ACT>   // ACT: the RSSM layers' activation; the actor trunk is ELU
 __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) char lds32[];
   const int Hm = p.Hm, N = p.N, A = p.A, D = p.D, Hd = p.Hd, S = p.S, C = p.C;
@@ -95,10 +95,10 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
   }
   __syncthreads();
 
-  // A 200-wide ELU layer: the accumulator starts from the bias (requested with the weight window, a layer ahead); the
+  // A 200-wide activated layer (actc: REPO_ACT_*, a compile-time tag): the accumulator starts from the bias (requested with the weight window, a layer ahead); the
   // epilogue splits the activations into the next layer's planes.  A quad exists in the tile iff its first column is
-  // below the tile's padded width: a wave-uniform test (columns [N, width) hold elu(0) = 0 and meet zero weights).
-  auto dense = [&](auto nb, const char* Xt, int psx, Win32& w, char* dst) __attribute__((always_inline)) {
+  // below the tile's padded width: a wave-uniform test (columns [N, width) hold act(0) = 0 and meet zero weights).
+  auto dense = [&](auto actc, auto nb, const char* Xt, int psx, Win32& w, char* dst) __attribute__((always_inline)) {
     if (w.act) {
       f32x16v c = bias_acc(w);
       wrun32<decltype(nb)::value, kPD32>(c, Xt + xf, psx, w, rw);
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
           const f32x4v a = quad(c, i);
           f32x4v v;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = elu(a[r]);
+          for (int r = 0; r < 4; ++r) v[r] = act_fn<decltype(actc)::value>(a[r]);
           stq32(dst, psH, c0 + 8 * i, li, v);
         }
       }
@@ -136,6 +136,8 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
                               int busy) __attribute__((always_inline)) {
     if (wave >= busy) store_tile32(T, ps, ncols, dst + first_row * ld, (unsigned)r0, nr, ld, 0u, lane, wave - busy, kW - busy);
   };
+  const std::integral_constant<int, REPO_ACT_ELU> actA{};   // the actor trunk: always ELU (dreamer.py:99-105)
+  const std::integral_constant<int, ACT> actR{};            // the RSSM layers
   const std::integral_constant<int, BF> nbF{};
   const std::integral_constant<int, BW> nbW{};
   const std::integral_constant<int, BX> nbX{};
@@ -150,19 +152,19 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
     const size_t tN = (size_t)t * N;
     // ---------------- actor trunk
     dopen32<BW>(wb, rw, p.aW[1], p.aB[1], Hd, wave, lane);
-    dense(nbF, Fp, psF, wa, HA);
+    dense(actA, nbF, Fp, psF, wa, HA);
     lds_barrier();
     save_tile(HA, psH, Hd, p.a_hidden, (unsigned)Hd, 0 * rowsAll + tN);
     dopen32<BW>(wa, rw, p.aW[2], p.aB[2], Hd, wave, lane);
-    dense(nbW, HA, psH, wb, HB);
+    dense(actA, nbW, HA, psH, wb, HB);
     lds_barrier();
     save_tile(HB, psH, Hd, p.a_hidden, (unsigned)Hd, 1 * rowsAll + tN);
     dopen32<BW>(wb, rw, p.aW[3], p.aB[3], Hd, wave, lane);
-    dense(nbW, HB, psH, wa, HA);
+    dense(actA, nbW, HB, psH, wa, HA);
     lds_barrier();
     save_tile(HA, psH, Hd, p.a_hidden, (unsigned)Hd, 2 * rowsAll + tN);
     dopen32<BW>(wa, rw, p.aW[4], p.aB[4], 2 * A, wave, lane);
-    dense(nbW, HA, psH, wb, HB);
+    dense(actA, nbW, HA, psH, wb, HB);
     lds_barrier();
     save_tile_shared(HB, psH, Hd, p.a_hidden, (unsigned)Hd, 3 * rowsAll + tN, 1);   // beside the head (wave 0)
     dopen32<BX>(wb, rw, p.Wsa, p.Bsa, D, wave, lane);
@@ -194,9 +196,9 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
       if (row < nr) p.xsa[(rb + row) * XL + k] = v;
     }
     lds_barrier();
-    // ---------------- e = elu(W_sa x + b); the GRU's first stream is opened behind it
+    // ---------------- e = act(W_sa x + b); the GRU's first stream is opened behind it
     wopen32<2 * BW, kPD32>(wa, rw, gact, p.Wg[0], p.Br, D, gtile, lane);
-    dense(nbX, XS, psX, wb, HA);
+    dense(actR, nbX, XS, psX, wb, HA);
     lds_barrier();
     save_tile(HA, psH, D, p.e, (unsigned)D, tN);
     // ---------------- GRU: one column tile per wave, gate by gate (three live accumulators at most).  A gate's two
@@ -277,7 +279,7 @@ __global__ __launch_bounds__(512) void imagine32_fwd_kernel(Img32FwdArgs p) {
     // ---------------- prior head (its first layer reads the belief columns of the feature tile: the rows of the
     //                  pack behind K = D are zero)
     dopen32<BW>(wb, rw, p.Wsp, p.Bsp, 2 * S, wave, lane);
-    dense(nbW, Fp, psF, wa, HB);
+    dense(actR, nbW, Fp, psF, wa, HB);
     lds_barrier();
     save_tile_shared(HB, psH, Hd, p.hp, (unsigned)Hd, tN, 2);   // beside the prior head's output layer (waves 0, 1)
     dopen32<BF>(wa, rw, p.aW[0], p.aB[0], Hd, wave, lane);  // the next step's first layer
@@ -320,7 +322,7 @@ struct Img32BwdArgs {
   float *d_araw, *dfeat0;
 };
 
-template <int BW, int BS2>   // BS2: 16-k blocks of 2 S
+template <int BW, int BS2, int ACT>   // BS2: 16-k blocks of 2 S
 __global__ __launch_bounds__(512) void imagine32_bwd_kernel(Img32BwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) char lds32[];
   const int Hm = p.Hm, N = p.N, A = p.A, D = p.D, Hd = p.Hd, S = p.S;
@@ -414,7 +416,7 @@ __global__ __launch_bounds__(512) void imagine32_bwd_kernel(Img32BwdArgs p) {
       }
     }
     lds_barrier();
-    // ---- XB = (d out @ W_sp) * elu'(hp)
+    // ---- XB = (d out @ W_sp) * act'(hp)
     wopen32<BW, kPDb, false>(wa, rw, wave < ntD, p.Wbp, 0, D, min(wave, ntD - 1), lane);
     if (wc.act) {
       f32x4v h[4];
@@ -428,7 +430,7 @@ __global__ __launch_bounds__(512) void imagine32_bwd_kernel(Img32BwdArgs p) {
           const f32x4v a = quad(c, i);
           f32x4v v;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = (c0 + 8 * i < Hd) ? a[r] * elu_grad_from_out(h[i][r]) : 0.f;
+          for (int r = 0; r < 4; ++r) v[r] = (c0 + 8 * i < Hd) ? a[r] * act_grad_from_out<ACT>(h[i][r]) : 0.f;
           stq32(XB, psH, c0 + 8 * i, li, v);
         }
       }
@@ -523,7 +525,7 @@ __global__ __launch_bounds__(512) void imagine32_bwd_kernel(Img32BwdArgs p) {
             const f32x4v a = quad(ae, i);
             f32x4v v;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = (c0 + 8 * i < D) ? a[r] * elu_grad_from_out(ev[i][r]) : 0.f;
+            for (int r = 0; r < 4; ++r) v[r] = (c0 + 8 * i < D) ? a[r] * act_grad_from_out<ACT>(ev[i][r]) : 0.f;
             stq32(XA, psH, c0 + 8 * i, li, v);  // d pre-activation of fc_embed_state_action
           }
         }
@@ -592,7 +594,7 @@ int imagine32_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64
                   NoiseSrc eps_act, NoiseSrc eps_prior, float min_std, float a_min_std, float a_init_std,
                   float a_mean_scale, float* featx, float* prior_mean, float* prior_std, float* a_hidden,
                   int64_t a_layer_rows, float* a_raw, float* a_mean, float* a_std, float* xsa, float* e, float* gates,
-                  float* hp, void* ws, hipStream_t stream) {
+                  float* hp, void* ws, hipStream_t stream, int act) {
   const int F = (int)(D + S + C), X = (int)(S + A + C);
   char* w = (char*)ws;
   char* const w_begin = w;
@@ -645,7 +647,7 @@ int imagine32_fwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64
   a.a_layer_rows = (size_t)a_layer_rows;
   a.gates_bytes = (unsigned)((size_t)Hm * N * 4 * D * sizeof(float));
   constexpr int lds_b = 3 * 1024 * kBF32 + 6 * 1024 * kBW32 + 3 * 1024 * kBX32 + 64 * kR32 * 4;
-  auto kern = imagine32_fwd_kernel<kBF32, kBW32, kBX32>;
+  auto kern = act == REPO_ACT_RELU ? imagine32_fwd_kernel<kBF32, kBW32, kBX32, REPO_ACT_RELU> : imagine32_fwd_kernel<kBF32, kBW32, kBX32, REPO_ACT_ELU>;
   hipError_t he = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);
   if (he != hipSuccess) return (int)he;
   hipLaunchKernelGGL(kern, dim3((unsigned)((N + kR32 - 1) / kR32)), dim3(512), lds_b, stream, a);
@@ -661,7 +663,7 @@ int imagine32_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64
                   NoiseSrc eps_act, NoiseSrc eps_prior, float min_std, float a_min_std, float a_mean_scale,
                   const float* featx, const float* prior_std, const float* a_mean, const float* a_std, const float* xsa,
                   const float* e, const float* gates, const float* hp, const float* dfeat, const float* dprior_mean,
-                  const float* dprior_std, float* d_araw, float* dfeat0, void* ws, hipStream_t stream) {
+                  const float* dprior_std, float* d_araw, float* dfeat0, void* ws, hipStream_t stream, int act) {
   const int X = (int)(S + A);
   char* w = (char*)ws;
   char* const w_begin = w;
@@ -696,7 +698,7 @@ int imagine32_bwd(int64_t Hm, int64_t N, int64_t A, int64_t D, int64_t Hd, int64
   a.d_araw = d_araw, a.dfeat0 = dfeat0;
   constexpr int kBS2 = 4;
   constexpr int lds_b = 6 * 1024 * kBW32 + 3 * 1024 * kBS2 + (16 * kBW32 + 32 + 48) * kR32 * 4;
-  auto kern = imagine32_bwd_kernel<kBW32, kBS2>;
+  auto kern = act == REPO_ACT_RELU ? imagine32_bwd_kernel<kBW32, kBS2, REPO_ACT_RELU> : imagine32_bwd_kernel<kBW32, kBS2, REPO_ACT_ELU>;
   hipError_t he = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);
   if (he != hipSuccess) return (int)he;
   hipLaunchKernelGGL(kern, dim3((unsigned)((N + kR32 - 1) / kR32)), dim3(512), lds_b, stream, a);

@@ -1,6 +1,6 @@
 // Fused dense heads (reward / value / actor MLPs): the whole layer chain of a row tile in ONE kernel.
 //
-// A head is in_dim -> hidden (ELU) x (L-1) -> out_dim.  Layer by layer through the GEMM engine every hidden
+// A head is in_dim -> hidden (ELU or ReLU: REPO_ACT_*, a template parameter) x (L-1) -> out_dim.  Layer by layer through the GEMM engine every hidden
 // activation is written to HBM and read back by the next launch, and a 200-wide layer is too small a GEMM to fill
 // the chip (0.35-0.4 of the fp32 MFMA peak in isolation, 4-5 launches per call).  Here a (persistent) workgroup takes
 // 16 or 32 rows at a time through the whole chain: activations stay in LDS (k4-interleaved tiles, rowtile.h), weights stream from L2 as packed
@@ -150,7 +150,7 @@ struct NextTile {
 // vw: this wave's (rotated) column-tile owner index.  The tile's rows are in Ta on entry (k4-interleaved; padding k
 // holds finite values and meets zero weight rows); layer l reads Ta / Tb alternately, so the buffer the last layer
 // does NOT read is free for the next tile's rows while the (narrow) output layer runs.
-template <int BI, int BH, int L, int RB, int TS>
+template <int BI, int BH, int L, int RB, int TS, int ACT>
 __device__ __forceinline__ void mlp_fwd_tile(const MlpFwdArgs& p, float* Ta, float* Tb, __amdgpu_buffer_rsrc_t rw,
                                              __amdgpu_buffer_rsrc_t rx,
                                              int r0, int nr, NextTile nx, int vw, int wave, int lane, int tile_no) {
@@ -200,7 +200,7 @@ __device__ __forceinline__ void mlp_fwd_tile(const MlpFwdArgs& p, float* Ta, flo
             } else {  // hidden % 4 == 0: the quad is whole
               f32x4v v;
 #pragma unroll
-              for (int r = 0; r < 4; ++r) v[r] = elu(acc[rb][t][r] + bv[t][r]);
+              for (int r = 0; r < 4; ++r) v[r] = act_fn<ACT>(acc[rb][t][r] + bv[t][r]);
               *reinterpret_cast<f32x4v*>(dst + rb * TS + ai(n0, m)) = v;
               if (row < nr) *reinterpret_cast<f32x4v*>(p.hid[l] + (size_t)(r0 + row) * Hd + n0) = v;
             }
@@ -215,7 +215,7 @@ __device__ __forceinline__ void mlp_fwd_tile(const MlpFwdArgs& p, float* Ta, flo
   }
 }
 
-template <int BI, int BH, int L>
+template <int BI, int BH, int L, int ACT = REPO_ACT_ELU>
 __global__ __launch_bounds__(512, 4) void mlp_fwd_kernel(MlpFwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int TS = 16 * (BI > BH ? BI : BH) * kR;  // floats per 16-row tile
@@ -245,9 +245,9 @@ __global__ __launch_bounds__(512, 4) void mlp_fwd_kernel(MlpFwdArgs p) {
     NextTile nx{mb.first * kR, 0};
     if (mb.count > 0) nx.nr = min((mb.count >= 2 ? 2 : 1) * kR, p.rows - nx.r0);
     if (rb == 2)
-      mlp_fwd_tile<BI, BH, L, 2, TS>(p, Ta, Tb, rw, rx, r0, min(2 * kR, p.rows - r0), nx, vw, wave, lane, tile_no);
+      mlp_fwd_tile<BI, BH, L, 2, TS, ACT>(p, Ta, Tb, rw, rx, r0, min(2 * kR, p.rows - r0), nx, vw, wave, lane, tile_no);
     else
-      mlp_fwd_tile<BI, BH, L, 1, TS>(p, Ta, Tb, rw, rx, r0, min(kR, p.rows - r0), nx, vw, wave, lane, tile_no);
+      mlp_fwd_tile<BI, BH, L, 1, TS, ACT>(p, Ta, Tb, rw, rx, r0, min(kR, p.rows - r0), nx, vw, wave, lane, tile_no);
     ++tile_no;
     if (L & 1) {  // the next tile's rows went where an odd chain's last layer does not read
       float* t = Ta;
@@ -257,9 +257,9 @@ __global__ __launch_bounds__(512, 4) void mlp_fwd_kernel(MlpFwdArgs p) {
   }
 }
 
-// stage s = 0 .. L-1 handles layer l = L-1-s: T = D_l * W_l; s < L-1: D_{l-1} = T * elu'(h_{l-1}); s = L-1: dx = T.
+// stage s = 0 .. L-1 handles layer l = L-1-s: T = D_l * W_l; s < L-1: D_{l-1} = T * act'(h_{l-1}); s = L-1: dx = T.
 // BO: 16-k blocks of out_dim.
-template <int BI, int BH, int BO, int L, int RB, int TS>
+template <int BI, int BH, int BO, int L, int RB, int TS, int ACT>
 __device__ __forceinline__ void mlp_bwd_tile(const MlpBwdArgs& p, float* T0, float* T1, __amdgpu_buffer_rsrc_t rw,
                                              int r0, int nr, int vw, int tid) {
   const int lane = tid & 63, lq = lane >> 4;
@@ -327,7 +327,7 @@ __device__ __forceinline__ void mlp_bwd_tile(const MlpBwdArgs& p, float* T0, flo
             } else {
               f32x4v g;
 #pragma unroll
-              for (int r = 0; r < 4; ++r) g[r] = acc[rb][t][r] * elu_grad_from_out(hv[rb][t][r]);
+              for (int r = 0; r < 4; ++r) g[r] = acc[rb][t][r] * act_grad_from_out<ACT>(hv[rb][t][r]);
               *reinterpret_cast<f32x4v*>(dst + rb * TS + ai(n0, m)) = g;
               float* sv = p.dsave[l > 0 ? l - 1 : 0];
               if (sv && row < nr) *reinterpret_cast<f32x4v*>(sv + (size_t)(r0 + row) * Hd + n0) = g * swr[rb];
@@ -340,7 +340,7 @@ __device__ __forceinline__ void mlp_bwd_tile(const MlpBwdArgs& p, float* T0, flo
   }
 }
 
-template <int BI, int BH, int BO, int L>
+template <int BI, int BH, int BO, int L, int ACT = REPO_ACT_ELU>
 __global__ __launch_bounds__(512, 4) void mlp_bwd_kernel(MlpBwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int TS = 16 * (BH > BO ? BH : BO) * kR;
@@ -358,10 +358,10 @@ __global__ __launch_bounds__(512, 4) void mlp_bwd_kernel(MlpBwdArgs p) {
     int tid = tid0;
     asm volatile("" : "+v"(tid));  // per-tile lane arithmetic stays inside the tile: hoisted out of this loop it spills
     if (mb.count >= 2) {
-      mlp_bwd_tile<BI, BH, BO, L, 2, TS>(p, T0, T1, rw, r0, min(2 * kR, p.rows - r0), vw, tid);
+      mlp_bwd_tile<BI, BH, BO, L, 2, TS, ACT>(p, T0, T1, rw, r0, min(2 * kR, p.rows - r0), vw, tid);
       mb.first += 2, mb.count -= 2;
     } else {
-      mlp_bwd_tile<BI, BH, BO, L, 1, TS>(p, T0, T1, rw, r0, min(kR, p.rows - r0), vw, tid);
+      mlp_bwd_tile<BI, BH, BO, L, 1, TS, ACT>(p, T0, T1, rw, r0, min(kR, p.rows - r0), vw, tid);
       mb.first += 1, mb.count -= 1;
     }
     __syncthreads();
@@ -399,17 +399,17 @@ static int grid_for(int rows) {
   return nb < slots ? nb : slots;
 }
 
-template <int L>
+template <int L, int ACT>
 static int launch_fwd(const MlpFwdArgs& a, hipStream_t s) {
   constexpr int lds = 4 * 16 * (kBI > kBH ? kBI : kBH) * kR * 4;
-  hipLaunchKernelGGL((mlp_fwd_kernel<kBI, kBH, L>), dim3(grid_for(a.rows)), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((mlp_fwd_kernel<kBI, kBH, L, ACT>), dim3(grid_for(a.rows)), dim3(512), lds, s, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? REPO_OK : (int)e;
 }
 
 int mlp_fused_fwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int L, const float* x, int64_t ldx,
                   const float* const* params, float* const* hidden_out, float* out, int64_t ldo, void* ws,
-                  hipStream_t stream) {
+                  hipStream_t stream, int act) {
   MlpFwdArgs a;
   a.trace = nullptr;
   a.rows = (int)rows, a.in_dim = (int)in_dim, a.hidden = (int)hidden, a.out_dim = (int)out_dim;
@@ -430,13 +430,14 @@ int mlp_fused_fwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim,
   a.wbytes = (unsigned)((w - a.wpack) * sizeof(float));
   int rc = launch_pack(pa, stream);
   if (rc) return rc;
-  return L == 4 ? launch_fwd<4>(a, stream) : launch_fwd<5>(a, stream);
+  if (act == REPO_ACT_RELU) return L == 4 ? launch_fwd<4, REPO_ACT_RELU>(a, stream) : launch_fwd<5, REPO_ACT_RELU>(a, stream);
+  return L == 4 ? launch_fwd<4, REPO_ACT_ELU>(a, stream) : launch_fwd<5, REPO_ACT_ELU>(a, stream);
 }
 
-template <int L>
+template <int L, int ACT>
 static int launch_bwd(const MlpBwdArgs& a, hipStream_t s) {
   constexpr int lds = 4 * 16 * kBH * kR * 4;
-  hipLaunchKernelGGL((mlp_bwd_kernel<kBI, kBH, 1, L>), dim3(grid_for(a.rows)), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((mlp_bwd_kernel<kBI, kBH, 1, L, ACT>), dim3(grid_for(a.rows)), dim3(512), lds, s, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? REPO_OK : (int)e;
 }
@@ -444,7 +445,7 @@ static int launch_bwd(const MlpBwdArgs& a, hipStream_t s) {
 // dsave[l], l < L-1: where the pre-activation gradient of hidden layer l goes (null: not kept)
 int mlp_fused_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int L, const float* const* params,
                   const float* const* hidden_acts, const float* dout, int64_t lddout, float* const* dsave, float* dx,
-                  int64_t lddx, int accumulate_dx, void* ws, hipStream_t stream, const float* dout_w, int64_t rows_w) {
+                  int64_t lddx, int accumulate_dx, void* ws, hipStream_t stream, int act, const float* dout_w, int64_t rows_w) {
   MlpBwdArgs a;
   a.dout_w = dout_w, a.rows_w = (int)rows_w;
   a.rows = (int)rows, a.in_dim = (int)in_dim, a.hidden = (int)hidden, a.out_dim = (int)out_dim;
@@ -469,7 +470,8 @@ int mlp_fused_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim,
   a.wbytes = (unsigned)((w - a.wpack) * sizeof(float));
   int rc = launch_pack(pa, stream);
   if (rc) return rc;
-  return L == 4 ? launch_bwd<4>(a, stream) : launch_bwd<5>(a, stream);
+  if (act == REPO_ACT_RELU) return L == 4 ? launch_bwd<4, REPO_ACT_RELU>(a, stream) : launch_bwd<5, REPO_ACT_RELU>(a, stream);
+  return L == 4 ? launch_bwd<4, REPO_ACT_ELU>(a, stream) : launch_bwd<5, REPO_ACT_ELU>(a, stream);
 }
 
 }  // namespace repo

@@ -17,6 +17,7 @@ struct ScanCsFwd {
   float min_std;
   float *featx, *post_mean, *post_std, *xsa, *e, *gates, *hq;
   unsigned* status;  // nullable: the caller's sticky status word (REPO_SCAN_STATUS_* bits)
+  int act;           // REPO_ACT_*: the dense activation (e and hq)
 };
 // packs the weights, clears the flags and launches the scan; eemb (the hoisted embed product) must be complete on `s`
 int scan_cs_fwd(const ScanCsFwd& a, void* ws, size_t ws_bytes, hipStream_t s);
@@ -34,6 +35,7 @@ struct ScanCsBwd {
   float *doutq, *dhq, *dgi, *dgh, *de;             // per-step deltas: (T,B,2S) (T,B,Hd) (T,B,3D) x2 (T,B,D)
   float *dprev_belief, *dprev_state;               // nullable
   unsigned* status;                                // nullable, as in ScanCsFwd
+  int act;                                         // REPO_ACT_* of the forward scan
 };
 // polls a spin-wait makes before giving up (1 << 22 unless repo_debug_scan_spin_limit changed it)
 int scan_cs_spin_limit();

@@ -9,10 +9,10 @@
 // (LDS holds activation tiles only, 57 / 67 KB, so the CU stays open to the convolutions of the other lanes: +0.9 % on the
 // update against LDS-resident slices, which were 4 % faster alone) -- and every workgroup carries the same 16
 // batch rows (one v_mfma_f32_16x16x4_f32 row tile; more rows = more independent groups of NW workgroups).  Per step:
-//   A  e = elu(W_sa x + b)                    all D columns, replicated                     (13 tiles x 3 blocks)
+//   A  e = act(W_sa x + b)                    all D columns, replicated                     (13 tiles x 3 blocks)
 //   B  GRU gates of the OWN 16 columns        K = D over e and over belief                  (6 x 13 blocks)
 //   X1 all-gather of the new belief           own slice published, NW slices gathered
-//   C  hq = elu(W_bq[:, :D] h + eemb + b)     own 16 columns, K split over the 4 waves      (13 blocks)
+//   C  hq = act(W_bq[:, :D] h + eemb + b)     own 16 columns, K split over the 4 waves      (13 blocks)
 //   X2 all-gather of hq
 //   D  posterior (mean, std) = W_sq hq + b    all 2S columns, replicated; sample            (4 tiles x 13 blocks)
 // An all-gather is the hand-off form measured by tools/probe/scan_exchange.hip (MI355X_MICROARCH.md's table, row 1):
@@ -87,7 +87,7 @@ __device__ __forceinline__ f32x4v mfma4(const f32x4v& w, const f32x4v& x, f32x4v
 }
 
 // KBX / KBD / KBH: 16-k blocks of X = S + A, of D, of Hd
-template <int KBX, int KBD, int KBH>
+template <int KBX, int KBD, int KBH, int ACT>
 __global__ __launch_bounds__(256) void observe_cs_fwd_kernel(CsFwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DP = KBD * 16, HP = KBH * 16, XP = KBX * 16;
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void observe_cs_fwd_kernel(CsFwdArgs p) {
       load_em(t + 1);
     }
     __syncthreads();
-    // ---- A: e = elu(W_sa x + b), every column tile (replicated in all workgroups); the own tile is saved
+    // ---- A: e = act(W_sa x + b), every column tile (replicated in all workgroups); the own tile is saved
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int tA = wave + 4 * j;
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void observe_cs_fwd_kernel(CsFwdArgs p) {
           acc = mfma4(WA[j][kb], *reinterpret_cast<const f32x4v*>(XS + ((kb * 4 + lq) * 16 + li) * 4), acc);
         f32x4v v;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = elu(acc[r] + bA[j][r]);
+        for (int r = 0; r < 4; ++r) v[r] = act_fn<ACT>(acc[r] + bA[j][r]);
         const int n0 = tA * 16 + 4 * lq;
         stq(ES, n0, li, v);
         if (tA == w && li < nr) {
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(256) void observe_cs_fwd_kernel(CsFwdArgs p) {
     }
     __syncthreads();
     if (!exchange(HS, 0, t, DP)) return poison();
-    // ---- C: hq = elu(W_bq[:, :D] h + eemb + b), own columns, K split over the waves
+    // ---- C: hq = act(W_bq[:, :D] h + eemb + b), own columns, K split over the waves
     {
       f32x4v acc = {0.f, 0.f, 0.f, 0.f};
       const int kb0 = (wave * KBD) / 4, kb1 = ((wave + 1) * KBD) / 4;
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256) void observe_cs_fwd_kernel(CsFwdArgs p) {
     __syncthreads();
     {
       const int o = erow * 16 + ecol;
-      const float v = elu(PART[o] + PART[256 + o] + PART[512 + o] + PART[768 + o] + em + b_q);
+      const float v = act_fn<ACT>(PART[o] + PART[256 + o] + PART[512 + o] + PART[768 + o] + em + b_q);
       QS[ai(ec, erow)] = v;
       if (erow < nr && ec < Hd) p.hq[(row0 + erow) * Hd + ec] = v;
     }
@@ -395,6 +395,7 @@ size_t scan_cs_fwd_ws_floats(int64_t B, int64_t A, int64_t D, int64_t Hd, int64_
 
 int scan_cs_fwd(const ScanCsFwd& q, void* ws, size_t ws_bytes, hipStream_t s) {
   if (!scan_cs_ok(q.T, q.B, q.A, q.D, q.Hd, q.S)) return REPO_E_SHAPE;
+  if (!act_ok(q.act)) return REPO_E_BADARG;
   if (!ws || ws_bytes < scan_cs_fwd_ws_floats(q.B, q.A, q.D, q.Hd, q.S) * sizeof(float)) return REPO_E_WS_TOO_SMALL;
   const int d = (int)q.D, h = (int)q.Hd, X = (int)(q.S + q.A), s2 = (int)(2 * q.S);
   const float* const* P = q.params;
@@ -446,10 +447,10 @@ int scan_cs_fwd(const ScanCsFwd& q, void* ws, size_t ws_bytes, hipStream_t s) {
   a.spin_limit = scan_cs_spin_limit();
   constexpr int DP = 208, HP = 208, XP = 48;
   const size_t lds_b = (size_t)(XP * 16 + 2 * DP * 16 + HP * 16 + 2 * 4 * 256 + 16 * 64 + 16 * 32) * sizeof(float);
-  he = hipFuncSetAttribute((const void*)observe_cs_fwd_kernel<3, 13, 13>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)lds_b);
+  auto kern = q.act == REPO_ACT_RELU ? observe_cs_fwd_kernel<3, 13, 13, REPO_ACT_RELU> : observe_cs_fwd_kernel<3, 13, 13, REPO_ACT_ELU>;
+  he = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
   if (he != hipSuccess) return (int)he;
-  hipLaunchKernelGGL((observe_cs_fwd_kernel<3, 13, 13>), dim3((unsigned)NW, (unsigned)G), dim3(256), lds_b, s, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)NW, (unsigned)G), dim3(256), lds_b, s, a);
   he = hipGetLastError();
   return he == hipSuccess ? REPO_OK : (int)he;
 }
@@ -457,12 +458,12 @@ int scan_cs_fwd(const ScanCsFwd& q, void* ws, size_t ws_bytes, hipStream_t s) {
 // ======================================================================================= reverse scan
 // The same column-split layout, walked backwards.  Workgroup w owns belief / hidden columns [16w, 16w+16):
 //   a  posterior output deltas (mean, raw std) from d state (upstream + carried), KL gradients    pointwise, replicated
-//   1  dhq = (W_sq^T d out) * elu'(hq)          all Hd columns, replicated (W_sq^T in registers)   13 tiles x 4 blocks
+//   1  dhq = (W_sq^T d out) * act'(hq)          all Hd columns, replicated (W_sq^T in registers)   13 tiles x 4 blocks
 //   2  d belief = carried + upstream + prior share + W_bq^T dhq   own columns, K split over waves  13 blocks
 //   d  GRU pointwise: d gates of the own columns; carried d belief = d belief * z
 //   X1 all-gather of (g_r, g_z, g_n, g_hn)      four tiles
 //   3  d belief_{t-1} += W_hh^T d gh ; d e = W_ih^T d gi          own columns, K = 3D, K split     78 blocks
-//   X2 all-gather of d e_pre = d e * elu'(e)
+//   X2 all-gather of d e_pre = d e * act'(e)
 //   4  d state_{t-1} = (W_sa[:, :S]^T d e_pre) * nonterm          replicated (W_sa^T in registers) 2 tiles x 13 blocks
 // Every weight fragment is register-stationary (a lane keeps what it feeds the MFMAs with); LDS: the activation tiles.
 struct CsBwdArgs {
@@ -480,7 +481,7 @@ struct CsBwdArgs {
   int spin_limit;
 };
 
-template <int KBD, int KBH>
+template <int KBD, int KBH, int ACT>
 __global__ __launch_bounds__(256) void observe_cs_bwd_kernel(CsBwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DP = KBD * 16, HP = KBH * 16, KP = DP > HP ? DP : HP, TS = KP * 16;  // TS: floats of a tile
@@ -662,7 +663,7 @@ __global__ __launch_bounds__(256) void observe_cs_bwd_kernel(CsBwdArgs p) {
     }
     const float nt0 = in.nt[0], nt1 = in.nt[1];
     __syncthreads();
-    // ---- 1: dhq = (W_sq^T d out) * elu'(hq), every hidden tile (replicated); the own tile is saved.  Into G[3].
+    // ---- 1: dhq = (W_sq^T d out) * act'(hq), every hidden tile (replicated); the own tile is saved.  Into G[3].
     float* QD = G + 3 * TS;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -674,7 +675,7 @@ __global__ __launch_bounds__(256) void observe_cs_bwd_kernel(CsBwdArgs p) {
           acc = mfma4(W1[j][kb], *reinterpret_cast<const f32x4v*>(DO + ((kb * 4 + lq) * 16 + li) * 4), acc);
         f32x4v v;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = li < nr ? acc[r] * elu_grad_from_out(in.hq4[j][r]) : 0.f;
+        for (int r = 0; r < 4; ++r) v[r] = li < nr ? acc[r] * act_grad_from_out<ACT>(in.hq4[j][r]) : 0.f;
         const int n0 = tA * 16 + 4 * lq;
         stq(QD, n0, li, v);
         if (tA == w && li < nr) {
@@ -751,7 +752,7 @@ __global__ __launch_bounds__(256) void observe_cs_bwd_kernel(CsBwdArgs p) {
       const int o = erow * 16 + ecol;
       dh += PART[o] + PART[256 + o] + PART[512 + o] + PART[768 + o];
       const float ae = PART[1024 + o] + PART[1280 + o] + PART[1536 + o] + PART[1792 + o];
-      const float v = e_ok ? ae * elu_grad_from_out(in.ev) : 0.f;
+      const float v = e_ok ? ae * act_grad_from_out<ACT>(in.ev) : 0.f;
       if (e_ok) p.de[(row0 + erow) * D + ec] = v;
       G[ai(ec, erow)] = v;  // G[0] now carries d e_pre (the gate tiles are consumed: barrier above)
     }
@@ -796,6 +797,7 @@ size_t scan_cs_bwd_ws_floats(int64_t B, int64_t A, int64_t D, int64_t Hd, int64_
 
 int scan_cs_bwd(const ScanCsBwd& q, void* ws, size_t ws_bytes, hipStream_t s) {
   if (!scan_cs_ok(q.T, q.B, q.A, q.D, q.Hd, q.S) || q.T <= 0) return REPO_E_SHAPE;
+  if (!act_ok(q.act)) return REPO_E_BADARG;
   if (!ws || ws_bytes < scan_cs_bwd_ws_floats(q.B, q.A, q.D, q.Hd, q.S) * sizeof(float)) return REPO_E_WS_TOO_SMALL;
   const int d = (int)q.D, h = (int)q.Hd, X = (int)(q.S + q.A), s2 = (int)(2 * q.S);
   const float* const* P = q.params;
@@ -845,9 +847,10 @@ int scan_cs_bwd(const ScanCsBwd& q, void* ws, size_t ws_bytes, hipStream_t s) {
   a.spin_limit = scan_cs_spin_limit();
   constexpr int DP = 208, TS = 208 * 16;
   const size_t lds_b = (size_t)(4 * TS + 64 * 16 + 2 * 4 * 256 + 16 * 32) * sizeof(float);
-  he = hipFuncSetAttribute((const void*)observe_cs_bwd_kernel<13, 13>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
+  auto kern = q.act == REPO_ACT_RELU ? observe_cs_bwd_kernel<13, 13, REPO_ACT_RELU> : observe_cs_bwd_kernel<13, 13, REPO_ACT_ELU>;
+  he = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
   if (he != hipSuccess) return (int)he;
-  hipLaunchKernelGGL((observe_cs_bwd_kernel<13, 13>), dim3((unsigned)NW, (unsigned)G), dim3(256), lds_b, s, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)NW, (unsigned)G), dim3(256), lds_b, s, a);
   he = hipGetLastError();
   return he == hipSuccess ? REPO_OK : (int)he;
 }

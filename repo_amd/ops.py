@@ -14,6 +14,25 @@ import torch
 from ._lib import check, lib
 
 EPI_NONE, EPI_ELU, EPI_RELU, EPI_MUL_DELU, EPI_MUL_DRELU, EPI_MUL_MASK4, EPI_MUL_CMASK, EPI_FILM_RELU = 0, 1, 2, 3, 4, 5, 6, 7
+# dense activation of the RSSM / MLP-head kernels (REPO_ACT_*, include/repo_hip.h): config.dense_activation_function
+ACT_ELU, ACT_RELU = 0, 1
+DENSE_ACTIVATIONS = {"elu": ACT_ELU, "relu": ACT_RELU}
+
+
+def dense_act_id(name, what):
+    """The REPO_ACT_* id of an activation name; any other name raises and names the supported values."""
+    try:
+        return DENSE_ACTIVATIONS[name]
+    except (KeyError, TypeError):
+        raise NotImplementedError(
+            f"{what}: the HIP dense kernels are built for dense_activation_function 'elu' or 'relu', not {name!r}") from None
+
+
+def _saved_act(sv, act):
+    """A backward runs with the activation of its forward: `act` may only repeat what the saved state remembers."""
+    if act is not None and act != sv.act:
+        raise ValueError(f"backward asked for activation {act}, the forward ran with {sv.act}")
+    return sv.act
 
 # layer ids of repo_conv_* (include/repo_hip.h): 0..6 the reference's 64 x 64 stack, 7..12 the build-defined 128 x 128 one
 ENC1, ENC2, ENC3, ENC4, DEC2, DEC3, DEC4 = range(7)
@@ -482,11 +501,11 @@ def take_status_into(sticky, taken):
 class ObserveSaved:
     __slots__ = ("T", "B", "A", "D", "Hd", "S", "E", "featx", "prior_state", "prior_mean", "prior_std", "post_mean",
                  "post_std", "xsa", "e", "gates", "hp", "hq", "nonterms", "embeds", "eps_prior", "eps_post", "noise",
-                 "prior_ready", "cs")
+                 "prior_ready", "cs", "act")
 
 
 def rssm_observe_fwd(params, prev_belief, prev_state, actions, nonterms, embeds, eps_prior, eps_post, min_std=0.1,
-                     noise=(0, 0), prior_only=False, prior_stream=None):
+                     noise=(0, 0), prior_only=False, prior_stream=None, act=ACT_ELU):
     """params: list of the 14 TransitionModel tensors in state_dict order.  Time-major inputs.
     eps_prior = eps_post = None: the kernel draws its noise from Philox stream noise = (seed, offset).
     prior_stream: a side stream -- the scan then leaves the prior head out (it depends on belief_t only, not on the
@@ -499,6 +518,7 @@ def rssm_observe_fwd(params, prev_belief, prev_state, actions, nonterms, embeds,
     dev = actions.device
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
     sv = ObserveSaved()
+    sv.act = int(act)
     sv.T, sv.B, sv.A, sv.D, sv.Hd, sv.S, sv.E = T, B, A, D, Hd, S, E
     sv.featx = f(T + 1, B, D + S)
     sv.prior_state, sv.prior_mean, sv.prior_std = f(T, B, S), f(T, B, S), f(T, B, S)
@@ -523,14 +543,15 @@ def rssm_observe_fwd(params, prev_belief, prev_state, actions, nonterms, embeds,
               and (D + 15) // 16 == 13 and (Hd + 15) // 16 == 13 and (S + A + 15) // 16 == 3 and S <= 32 and D % 4 == 0)
     hoist = (prior_stream is not None or use_cs) and not prior_only
     check(
-        lib().repo_rssm_observe_fwd(
+        lib().repo_rssm_observe_fwd_act(
             T, B, A, D, Hd, S, E, pa, _ptr(_f32c(prev_belief)), _ptr(_f32c(prev_state)), _ptr(_f32c(actions)),
             _ptr(sv.nonterms), _ptr(sv.embeds), _ptr(sv.eps_prior), _ptr(sv.eps_post), sv.noise[0], sv.noise[1],
             float(min_std), _ptr(sv.featx), _ptr(sv.prior_state), _ptr(sv.prior_mean), _ptr(sv.prior_std), _ptr(sv.post_mean),
             _ptr(sv.post_std), _ptr(sv.xsa), _ptr(sv.e), _ptr(sv.gates), _ptr(sv.hp), _ptr(sv.hq), _ptr(eemb),
             3 if use_cs else 2 if hoist else int(prior_only), _ptr(scan_status(dev)), _ptr(ws), ws.numel(), _stream(),
+            sv.act,
         ),
-        "repo_rssm_observe_fwd",
+        "repo_rssm_observe_fwd_act",
     )
     sv.prior_ready = None
     sv.cs = use_cs   # the reverse scan takes the same engine
@@ -538,10 +559,10 @@ def rssm_observe_fwd(params, prev_belief, prev_state, actions, nonterms, embeds,
         nbp = lib().repo_rssm_prior_head_workspace_bytes(T, B, S)
         wsp = workspace(nbp, dev)
         check(
-            lib().repo_rssm_prior_head(T, B, D, Hd, S, pa, _ptr(sv.featx), _ptr(sv.eps_prior), sv.noise[0], sv.noise[1],
-                                       float(min_std), _ptr(sv.hp), _ptr(sv.prior_state), _ptr(sv.prior_mean),
-                                       _ptr(sv.prior_std), _ptr(wsp), nbp, _stream()),
-            "repo_rssm_prior_head",
+            lib().repo_rssm_prior_head_act(T, B, D, Hd, S, pa, _ptr(sv.featx), _ptr(sv.eps_prior), sv.noise[0],
+                                           sv.noise[1], float(min_std), _ptr(sv.hp), _ptr(sv.prior_state),
+                                           _ptr(sv.prior_mean), _ptr(sv.prior_std), _ptr(wsp), nbp, _stream(), sv.act),
+            "repo_rssm_prior_head_act",
         )
     elif hoist:
         main = torch.cuda.current_stream(dev)
@@ -550,10 +571,11 @@ def rssm_observe_fwd(params, prev_belief, prev_state, actions, nonterms, embeds,
         with torch.cuda.stream(prior_stream):
             wsp = torch.empty(nbp, dtype=torch.uint8, device=dev)  # its own scratch: the shared workspace is the main stream's
             check(
-                lib().repo_rssm_prior_head(T, B, D, Hd, S, pa, _ptr(sv.featx), _ptr(sv.eps_prior), sv.noise[0], sv.noise[1],
-                                           float(min_std), _ptr(sv.hp), _ptr(sv.prior_state), _ptr(sv.prior_mean),
-                                           _ptr(sv.prior_std), _ptr(wsp), nbp, prior_stream.cuda_stream),
-                "repo_rssm_prior_head",
+                lib().repo_rssm_prior_head_act(T, B, D, Hd, S, pa, _ptr(sv.featx), _ptr(sv.eps_prior), sv.noise[0],
+                                               sv.noise[1], float(min_std), _ptr(sv.hp), _ptr(sv.prior_state),
+                                               _ptr(sv.prior_mean), _ptr(sv.prior_std), _ptr(wsp), nbp,
+                                               prior_stream.cuda_stream, sv.act),
+                "repo_rssm_prior_head_act",
             )
         for t in (sv.hp, sv.prior_state, sv.prior_mean, sv.prior_std):
             t.record_stream(prior_stream)
@@ -562,28 +584,31 @@ def rssm_observe_fwd(params, prev_belief, prev_state, actions, nonterms, embeds,
 
 
 def rssm_observe_bwd(params, sv, dparams, dfeat=None, dprior_state=None, dpm=None, dps=None, dqm=None, dqs=None,
-                     dembeds=None, dprev_belief=None, dprev_state=None, accumulate=False, min_std=0.1):
+                     dembeds=None, dprev_belief=None, dprev_state=None, accumulate=False, min_std=0.1, act=None):
+    """act: None (the activation `sv` remembers from its forward) or that same value; another one raises."""
+    act = _saved_act(sv, act)
     dev = sv.featx.device
     nb = lib().repo_rssm_observe_bwd_workspace_bytes(sv.T, sv.B, sv.A, sv.D, sv.Hd, sv.S, sv.E)
     ws = workspace(nb, dev)
     pa, ga = ptr_array(params), ptr_array(dparams)
     check(
-        lib().repo_rssm_observe_bwd(
+        lib().repo_rssm_observe_bwd_act(
             sv.T, sv.B, sv.A, sv.D, sv.Hd, sv.S, sv.E, pa, _ptr(sv.nonterms), _ptr(sv.embeds), _ptr(sv.eps_prior),
             _ptr(sv.eps_post), sv.noise[0], sv.noise[1], float(min_std), _ptr(sv.featx), _ptr(sv.prior_std), _ptr(sv.post_std), _ptr(sv.xsa),
             _ptr(sv.e), _ptr(sv.gates), _ptr(sv.hp), _ptr(sv.hq), _ptr(dfeat), _ptr(dprior_state), _ptr(dpm),
             _ptr(dps), _ptr(dqm), _ptr(dqs), ga, _ptr(dembeds), _ptr(dprev_belief), _ptr(dprev_state),
             int(bool(accumulate)) | (2 if getattr(sv, "cs", False) else 0), _ptr(scan_status(dev)), _ptr(ws), ws.numel(),
-            _stream(),
+            _stream(), act,
         ),
-        "repo_rssm_observe_bwd",
+        "repo_rssm_observe_bwd_act",
     )
 
 
 # ----------------------------------------------------------------------------- MLP heads
-def mlp_fwd(params, x, out=None, hid=None):
+def mlp_fwd(params, x, out=None, hid=None, act=ACT_ELU):
     """params: [w1,b1,...,wL,bL]; x (rows, in_dim) view with contiguous rows.  Returns (out, hidden list).
-    `hid`: optional caller-provided (rows, hidden) buffers for the L-1 hidden activations."""
+    `hid`: optional caller-provided (rows, hidden) buffers for the L-1 hidden activations.
+    act: ACT_ELU / ACT_RELU between the layers."""
     L = len(params) // 2
     rows, in_dim = x.shape
     hidden = params[0].shape[0] if L > 1 else 0
@@ -597,15 +622,16 @@ def mlp_fwd(params, x, out=None, hid=None):
     nb = lib().repo_mlp_fwd_workspace_bytes(rows, in_dim, max(hidden, 1), out_dim, L)
     ws = workspace(nb, dev) if nb else None
     check(
-        lib().repo_mlp_fwd(rows, in_dim, max(hidden, 1), out_dim, L, _ptr(x), _ld(x), pa, ha, _ptr(out), _ld(out),
-                           _ptr(ws), nb, _stream()),
-        "repo_mlp_fwd",
+        lib().repo_mlp_fwd_act(rows, in_dim, max(hidden, 1), out_dim, L, _ptr(x), _ld(x), pa, ha, _ptr(out), _ld(out),
+                               _ptr(ws), nb, _stream(), int(act)),
+        "repo_mlp_fwd_act",
     )
     return out, hid
 
 
-def mlp_bwd(params, x, hid, dout, dparams=None, accumulate_w=False, dx=None, accumulate_dx=False, dout_w=None):
-    """dout_w (rows_w <= rows, 1): a scalar head differentiated for TWO losses in one reverse chain -- dx from `dout`
+def mlp_bwd(params, x, hid, dout, dparams=None, accumulate_w=False, dx=None, accumulate_dx=False, dout_w=None,
+            act=ACT_ELU):
+    """act: the activation `hid` was computed with (mlp_fwd's).  dout_w (rows_w <= rows, 1): a scalar head differentiated for TWO losses in one reverse chain -- dx from `dout`
     over all rows, dparams from `dout_w` over the first rows_w rows (include/repo_hip.h, repo_mlp_bwd)."""
     L = len(params) // 2
     rows, in_dim = x.shape
@@ -620,10 +646,10 @@ def mlp_bwd(params, x, hid, dout, dparams=None, accumulate_w=False, dx=None, acc
         rows_w = dout_w.shape[0]
         assert dout_w.is_contiguous() and dout_w.numel() == rows_w and dout.shape[1] == 1
     check(
-        lib().repo_mlp_bwd(rows, in_dim, hidden, out_dim, L, _ptr(x), _ld(x), pa, ha, _ptr(dout), _ld(dout), ga,
-                           int(accumulate_w), _ptr(dx), _ld(dx) if dx is not None else 0, int(accumulate_dx),
-                           _ptr(dout_w), rows_w, _ptr(ws), ws.numel(), _stream()),
-        "repo_mlp_bwd",
+        lib().repo_mlp_bwd_act(rows, in_dim, hidden, out_dim, L, _ptr(x), _ld(x), pa, ha, _ptr(dout), _ld(dout), ga,
+                               int(accumulate_w), _ptr(dx), _ld(dx) if dx is not None else 0, int(accumulate_dx),
+                               _ptr(dout_w), rows_w, _ptr(ws), ws.numel(), _stream(), int(act)),
+        "repo_mlp_bwd_act",
     )
 
 
@@ -666,12 +692,15 @@ def actor_head_bwd(mean, std, dmean=None, dstd=None, daction=None, action=None, 
 # ----------------------------------------------------------------------------- imagination
 class ImagineSaved:
     __slots__ = ("Hm", "N", "A", "D", "Hd", "S", "featx", "prior_mean", "prior_std", "a_hidden", "a_raw", "a_mean",
-                 "a_std", "xsa", "e", "gates", "hp", "eps_act", "eps_prior", "noise", "C")
+                 "a_std", "xsa", "e", "gates", "hp", "eps_act", "eps_prior", "noise", "C", "act")
 
 
 def rssm_imagine_fwd(rssm_params, actor_params, belief0, state0, eps_act, eps_prior, min_std=0.1, a_min_std=0.1,
-                     a_init_std=0.0, a_mean_scale=5.0, spare_slot=False, noise=(0, 0), horizon=None, cond=None):
-    """spare_slot: allocate the saved actor tensors with one extra step slot ((Hm+1)*N rows) so the
+                     a_init_std=0.0, a_mean_scale=5.0, spare_slot=False, noise=(0, 0), horizon=None, cond=None,
+                     act=ACT_ELU):
+    """act: the activation of the RSSM part of a step; the actor trunk inside the rollout is always ELU (the reference
+    never hands ActorModel the config's activation: dreamer.py:99-105).
+    spare_slot: allocate the saved actor tensors with one extra step slot ((Hm+1)*N rows) so the
     caller can evaluate the actor on the final imagined state into the same buffers.
     eps_act = eps_prior = None (+ horizon = Hm): the kernel draws its noise from Philox stream noise = (seed, offset).
     cond (N, C): the multitask agents' conditioned rollout (include/repo_hip.h); the actor's fc1 and W_sa carry C more
@@ -687,6 +716,7 @@ def rssm_imagine_fwd(rssm_params, actor_params, belief0, state0, eps_act, eps_pr
     dev = belief0.device
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
     sv = ImagineSaved()
+    sv.act = int(act)
     sv.Hm, sv.N, sv.A, sv.D, sv.Hd, sv.S = Hm, N, A, D, Hd, S
     sv.C = C
     sv.featx = f(Hm + 1, N, D + S)
@@ -702,20 +732,21 @@ def rssm_imagine_fwd(rssm_params, actor_params, belief0, state0, eps_act, eps_pr
     ws = workspace(nb, dev)
     ra, aa = ptr_array(rssm_params), ptr_array(actor_params)
     check(
-        lib().repo_rssm_imagine_fwd(
+        lib().repo_rssm_imagine_fwd_act(
             Hm, N, A, D, Hd, S, La, ra, aa, _ptr(_f32c(belief0)), _ptr(_f32c(state0)),
             _ptr(_f32c(cond)) if C else None, C, _ptr(sv.eps_act),
             _ptr(sv.eps_prior), sv.noise[0], sv.noise[1], min_std, a_min_std, a_init_std, a_mean_scale, _ptr(sv.featx), _ptr(sv.prior_mean),
             _ptr(sv.prior_std), _ptr(sv.a_hidden), ar, _ptr(sv.a_raw), _ptr(sv.a_mean), _ptr(sv.a_std), _ptr(sv.xsa),
-            _ptr(sv.e), _ptr(sv.gates), _ptr(sv.hp), _ptr(ws), ws.numel(), _stream(),
+            _ptr(sv.e), _ptr(sv.gates), _ptr(sv.hp), _ptr(ws), ws.numel(), _stream(), sv.act,
         ),
-        "repo_rssm_imagine_fwd",
+        "repo_rssm_imagine_fwd_act",
     )
     return sv
 
 
 def rssm_imagine_bwd(rssm_params, sv, dfeat, dprior_mean=None, dprior_std=None, want_dfeat0=False, min_std=0.1,
-                     a_min_std=0.1, a_mean_scale=5.0, d_araw=None):
+                     a_min_std=0.1, a_mean_scale=5.0, d_araw=None, act=None):
+    act = _saved_act(sv, act)   # None: the forward's
     dev = dfeat.device
     if d_araw is None:
         d_araw = torch.empty(sv.Hm * sv.N, 2 * sv.A, dtype=torch.float32, device=dev)
@@ -724,13 +755,13 @@ def rssm_imagine_bwd(rssm_params, sv, dfeat, dprior_mean=None, dprior_std=None, 
     ws = workspace(nb, dev)
     ra = ptr_array(rssm_params)
     check(
-        lib().repo_rssm_imagine_bwd(
+        lib().repo_rssm_imagine_bwd_act(
             sv.Hm, sv.N, sv.A, sv.D, sv.Hd, sv.S, getattr(sv, "C", 0), ra, _ptr(sv.eps_act), _ptr(sv.eps_prior),
             sv.noise[0], sv.noise[1], min_std, a_min_std, a_mean_scale, _ptr(sv.featx), _ptr(sv.prior_std), _ptr(sv.a_mean), _ptr(sv.a_std), _ptr(sv.xsa),
             _ptr(sv.e), _ptr(sv.gates), _ptr(sv.hp), _ptr(_f32c(dfeat)), _ptr(dprior_mean), _ptr(dprior_std),
-            _ptr(d_araw), _ptr(dfeat0), _ptr(ws), ws.numel(), _stream(),
+            _ptr(d_araw), _ptr(dfeat0), _ptr(ws), ws.numel(), _stream(), act,
         ),
-        "repo_rssm_imagine_bwd",
+        "repo_rssm_imagine_bwd_act",
     )
     return d_araw, dfeat0
 
