@@ -24,6 +24,7 @@
 #pragma once
 #include <type_traits>
 
+#include "dense_epi.h"
 #include "vgemm.h"
 
 namespace repo {
@@ -48,12 +49,8 @@ __device__ __forceinline__ void bg_split3(float x0, float x1, unsigned& p1, unsi
 
 struct BgArgs {
   Dense2D A, B;  // A: [M][K] if A_KC else [K][M];  B: [N][K] if B_KC else [K][N]
-  const float* bias;
-  const float* aux;
-  float* C;
-  int ldc, ldaux, bias_div;
+  DenseEpi e;
   int M, N, K;
-  int epi, accumulate;
 };
 
 template <int BM_, int BN_, int BK_>
@@ -303,27 +300,7 @@ __global__ __launch_bounds__(512) void bgemm_kernel(BgArgs p) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int n = n0 + (wn * TN + j) * 32 + li;
-      if (n >= p.N) continue;
-      const float bv = p.bias ? p.bias[p.bias_div > 1 ? n / p.bias_div : n] : 0.f;   // bias_div < 0: one bias per output column
-      const int mb = m0 + (wm * TM + i) * 32 + 4 * lh;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = mb + (e & 3) + 8 * (e >> 2);
-        if (m < p.M) {
-          float v = acc[i][j][e] + bv;
-          if (p.epi == REPO_EPI_ELU) v = elu(v);
-          else if (p.epi == REPO_EPI_RELU) v = fmaxf(v, 0.f);
-          else if (p.epi == REPO_EPI_MUL_DELU) v *= elu_grad_from_out(p.aux[(size_t)m * p.ldaux + n]);
-          else if (p.epi == REPO_EPI_MUL_DRELU) v = p.aux[(size_t)m * p.ldaux + n] > 0.f ? v : 0.f;
-          else if (p.epi == REPO_EPI_FILM_RELU) {   // row m's FiLM table: [scale (C) | shift (C)], C = ldaux / 2, channel n / bias_div
-            const int ch = p.bias_div == 1 ? n : n / (p.bias_div < 0 ? -p.bias_div : p.bias_div);
-            v = fmaxf(fmaf(p.aux[(size_t)m * p.ldaux + ch], v, p.aux[(size_t)m * p.ldaux + (p.ldaux >> 1) + ch]), 0.f);
-          }
-          float* c = p.C + (size_t)m * p.ldc + n;
-          if (p.accumulate) v += *c;
-          *c = v;
-        }
-      }
+      if (n < p.N) p.e.store_col<false>(m0 + (wm * TM + i) * 32 + 4 * lh, n, acc[i][j], p.M);
     }
 }
 
@@ -331,7 +308,8 @@ typedef BgTile<256, 128, 16> BgBig;
 typedef BgTile<128, 128, 32> BgMid;
 
 // Shapes this engine takes (everything else stays on the fp32-MFMA tile engines): big products whose tiles fill the
-// chip, 16-byte aligned operands with leading dimensions that keep every staged vector aligned.
+// chip, 16-byte aligned operands with leading dimensions that keep every staged vector aligned.  Asked by gemm.hip's
+// dense_plan only, which also picks the tile.
 #ifndef BG_MIN_TILES
 #define BG_MIN_TILES 150   // (A/B builds: tools/build_variant.sh; 100 -- the 128 x 128 stack's fc at 1568 rows makes 104 tiles -- measured neutral: 12.94-12.99 against 12.90-13.02 ms per update, round 6)
 #endif
@@ -354,14 +332,6 @@ static int launch_bgemm(const BgArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((bgemm_kernel<T, A_KC, B_KC>), dim3((unsigned)(gx * gy)), dim3(512), T::LDS_BYTES, s, a);
   he = hipGetLastError();
   return he == hipSuccess ? REPO_OK : (int)he;
-}
-
-template <bool A_KC, bool B_KC>
-static int bgemm_dispatch(const BgArgs& a, hipStream_t s) {
-  // 256 x 128 tiles when they alone fill the chip twice over, else 128 x 128 (K = 32 per stage)
-  const long big = (long)((a.M + 255) / 256) * ((a.N + 127) / 128);
-  if (big >= 400) return launch_bgemm<BgBig, A_KC, B_KC>(a, s);
-  return launch_bgemm<BgMid, A_KC, B_KC>(a, s);
 }
 
 }  // namespace repo

@@ -199,7 +199,7 @@ def _aligned(t):
 
 def _nt_pays(M, N, K, *operands):
     """The transposing copy is made only for a product the bf16x6 engine will take in its NT form (the same predicate as
-    the library's dispatch: repo_gemm_nt_pays -- sizes, enough tiles to fill the chip, this thread's repo_debug_bgemm)
+    the library's dispatch: repo_gemm_nt_pays asks csrc/gemm.hip's dense_plan -- sizes, enough tiles to fill the chip, this thread's repo_debug_bgemm)
     and only from operands repo_transpose and the engine accept; anything else -- N = 513, a misaligned view, a
     data-parallel shard whose 637 rows make 125 tiles -- stays on the untransposed fp32-MFMA forms."""
     return (min(M, N, K) >= _NT_MIN and _nt_forms() and all(_aligned(t) for t in operands)

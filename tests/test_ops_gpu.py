@@ -9,7 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.util import CONV_ENGINE_KERNELS, has, log, relerr, rnd, traced
+from tests.util import CONV_ENGINE_KERNELS, DENSE_ENGINE_KERNELS, has, log, relerr, rnd, traced
 
 pytestmark = pytest.mark.gpu
 
@@ -78,7 +78,7 @@ def test_gemm_strided_and_epilogues(ops):
 
 BG_SHAPES = [
     # (ta, tb, M, N, K): the decoder's three big products and ragged variants of each operand layout
-    (False, False, 2450, 3200, 1024),   # conv1 forward: h1 = h0 @ W1            (256 x 128 tiles)
+    (False, False, 2450, 3200, 1024),   # conv1 forward: h1 = h0 @ W1            (10 x 25 = 250 < 400 tiles of 256 x 128: 128 x 128 tiles)
     (False, True, 2450, 1024, 3200),    # conv1 data gradient: dh0 = d1 @ W1^T   (128 x 128 tiles, K 32 per stage)
     (True, False, 1024, 3200, 2450),    # conv1 weight gradient through repo_gemm's layout: A[k][m], B[k][n]
     (False, True, 1301, 1932, 1001),    # nothing divides anything: M, N ragged in the last tiles, K % 16 = 9, K % 4 = 1
@@ -128,6 +128,81 @@ def test_bgemm_matches_fp64_and_the_fp32_engine(ops, ta, tb, M, N, K):
         errs[engine] = float(((acc.double().cpu() - (opA @ opB + 0.5)).abs() / mag).max())
     log(f"bgemm ta={ta} tb={tb} {M}x{N}x{K}: max |err| / sum|a||b|  bf16x6 {errs[1]:.2e}  fp32 MFMA {errs[0]:.2e}")
     assert errs[1] <= 1.25 * errs[0] + 1e-9, errs
+
+
+def _tile(*cfg):
+    return r"TileCfg<" + r",\s*".join(str(c) for c in cfg) + ">"
+
+
+# (id, ta, tb, M, N, K, engine kernel, its instantiation): the smallest shape that reaches each engine and tile of
+# csrc/gemm.hip's dense_plan.  K = 36 / 20: vector loads; K = 17: odd, gathers; K = 130: the bf16x6 engine's shortest K,
+# 176 tiles of 128 x 128 (>= 150) and 20 x 20 = 400 tiles of 256 x 128 with both edges ragged.
+DENSE_ENGINE_CASES = [
+    ("gemv-nt", False, True, 5, 60, 200, "gemv_small_kernel", r"gemv_small_kernel<true>"),
+    ("gemv-nn", False, False, 5, 60, 200, "gemv_small_kernel", r"gemv_small_kernel<false>"),
+    ("vec-32x128", False, True, 20, 60, 36, "vgemm_kernel", r"vgemm_kernel<.*VGemmOp<.*" + _tile(1, 4, 1, 1, 16, 2)),
+    ("vec-64x64", False, True, 65, 129, 36, "vgemm_kernel", r"vgemm_kernel<.*VGemmOp<.*" + _tile(2, 2, 1, 1, 16, 2)),
+    ("vec-128x128s1", False, True, 1536, 2048, 20, "vgemm_kernel", r"vgemm_kernel<.*VGemmOp<.*" + _tile(2, 2, 2, 2, 16, 1)),
+    ("gather-32x128", False, True, 20, 60, 17, "igemm_kernel", r"igemm_kernel<.*GemmOp<.*" + _tile(1, 4, 1, 1, 16, 2)),
+    ("gather-64x64", False, True, 65, 129, 17, "igemm_kernel", r"igemm_kernel<.*GemmOp<.*" + _tile(2, 2, 1, 1, 16, 2)),
+    ("gather-128x128", False, True, 1536, 2048, 17, "igemm_kernel", r"igemm_kernel<.*GemmOp<.*" + _tile(2, 2, 2, 2, 16, 2)),
+    ("bf16-mid", False, False, 1300, 1940, 130, "bgemm_kernel", r"bgemm_kernel<.*BgTile<128,\s*128,\s*32>"),
+    ("bf16-big", False, True, 4865, 2450, 130, "bgemm_kernel", r"bgemm_kernel<.*BgTile<256,\s*128,\s*16>"),
+]
+
+
+@pytest.mark.parametrize("ta,tb,M,N,K,engine,kernel", [c[1:] for c in DENSE_ENGINE_CASES], ids=[c[0] for c in DENSE_ENGINE_CASES])
+def test_gemm_every_engine_every_epilogue(ops, ta, tb, M, N, K, engine, kernel):
+    """Every engine and tile dense_plan can choose, at the smallest shape that reaches it, with every epilogue it accepts,
+    against fp64 (TOL: the fp32-accumulation bound at the top of this file) -- and the device trace of each call lists
+    that engine's kernel and no other dense engine's.  k-contiguous operands, aux and the accumulate destination are
+    column slices of wider buffers (leading dimensions that differ from the extents)."""
+    rs = np.random.RandomState(M + 3 * N + 7 * K + tb)
+
+    def sliced(t, lead=0):      # t as columns [lead, lead + cols) of a buffer whose row pitch is a multiple of 4
+        wide = torch.zeros(t.shape[0], (lead + t.shape[1] + 7) // 4 * 4)
+        wide[:, lead : lead + t.shape[1]] = t
+        return dev(wide)[:, lead : lead + t.shape[1]]
+
+    A = rnd(rs, K, M) if ta else rnd(rs, M, K)
+    B = rnd(rs, N, K, scale=0.1) if tb else rnd(rs, K, N, scale=0.1)
+    prod = (A.double().t() if ta else A.double()) @ (B.double().t() if tb else B.double())
+    dA, dB = (dev(A) if ta else sliced(A)), (sliced(B) if tb else dev(B))
+    bias, bias25 = rnd(rs, N), rnd(rs, (N + 24) // 25)
+    b25 = bias25.double().repeat_interleave(25)[:N]
+    h = F.elu(rnd(rs, M, N))            # a saved ELU output: in (-1, inf), both signs
+    hr = F.relu(h)                      # a saved ReLU output
+    base = rnd(rs, M, N + 16)           # accumulate destination: columns [8, 8 + N) of it
+    C = (N + 24) // 25
+    table = torch.cat([1 + rnd(rs, M, C, scale=0.5), rnd(rs, M, C)], dim=1)      # FiLM: row m = [scale (C) | shift (C)]
+    scale, shift = (table[:, i * C : (i + 1) * C].double().repeat_interleave(25, dim=1)[:, :N] for i in (0, 1))
+
+    def check(what, want, **kw):
+        out = kw.get("out")
+        got, names = traced(lambda: ops.gemm(dA, dB, ta, tb, **kw))
+        e = relerr(got, want)
+        log(f"gemm engine {kernel} {M}x{N}x{K} {what}: relerr {e:.2e}")
+        assert e < TOL, (what, e)
+        assert has(names, kernel), (what, names)
+        assert not any(has(names, rf"\b{k}\b") for k in set(DENSE_ENGINE_KERNELS) - {engine}), (what, names)
+        return out
+
+    dbias = dev(bias)
+    check("none", prod + bias.double(), bias=dbias)
+    check("elu", F.elu(prod + bias.double()), bias=dbias, epi=ops.EPI_ELU)
+    check("relu", F.relu(prod + bias.double()), bias=dbias, epi=ops.EPI_RELU)
+    check("mul_delu", prod * torch.where(h > 0, torch.ones_like(h), h + 1).double(), epi=ops.EPI_MUL_DELU, aux=sliced(h, 3))
+    check("mul_drelu", prod * (hr > 0), epi=ops.EPI_MUL_DRELU, aux=sliced(hr, 3))
+    check("bias_div 25", F.relu(prod + b25), bias=dev(bias25), bias_div=25, epi=ops.EPI_RELU)
+    buf = dev(base)
+    check("accumulate", prod + base[:, 8 : 8 + N].double(), out=buf[:, 8 : 8 + N], accumulate=True)
+    assert torch.equal(buf[:, :8].cpu(), base[:, :8]) and torch.equal(buf[:, 8 + N :].cpu(), base[:, 8 + N :])
+    if engine != "gemv_small_kernel":   # (repo_gemm keeps FiLM off the <= 8-row kernel)
+        dtab = dev(table)
+        check("film, bias per channel", F.relu(scale * (prod + b25) + shift), bias=dev(bias25), bias_div=25,
+              epi=ops.EPI_FILM_RELU, aux=dtab)
+        check("film, bias per column", F.relu(scale * (prod + bias.double()) + shift), bias=dbias, bias_div=-25,
+              epi=ops.EPI_FILM_RELU, aux=dtab)
 
 
 def test_bgemm_weight_gradient_without_slabs(ops):

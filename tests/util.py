@@ -57,3 +57,7 @@ CONV_ENGINE_KERNELS = ("dconv_down_kernel", "bconv_down_kernel", "tconv_down_ker
                        "dconv_up_kernel", "tconv_up_kernel", "igemm_kernel", "dconv_wgrad_kernel", "bconv_wgrad_kernel",
                        "tconv_wgrad_kernel")
 CONV_REDUCE_KERNELS = ("conv_slab_reduce_kernel", "conv_slab_reduce_wave_kernel", "channel_sum_kernel")
+
+# One kernel per dense engine of repo_gemm (csrc/gemm.hip's dense_plan picks exactly one of them per call): the <= 8-row vector
+# kernel, the bf16x6 engine, and the fp32-MFMA tile engines with vector loads / with gathers.
+DENSE_ENGINE_KERNELS = ("gemv_small_kernel", "bgemm_kernel", "vgemm_kernel", "igemm_kernel")
