@@ -61,3 +61,10 @@ CONV_REDUCE_KERNELS = ("conv_slab_reduce_kernel", "conv_slab_reduce_wave_kernel"
 # One kernel per dense engine of repo_gemm (csrc/gemm.hip's dense_plan picks exactly one of them per call): the <= 8-row vector
 # kernel, the bf16x6 engine, and the fp32-MFMA tile engines with vector loads / with gathers.
 DENSE_ENGINE_KERNELS = ("gemv_small_kernel", "bgemm_kernel", "vgemm_kernel", "igemm_kernel")
+
+# Every kernel a dense weight gradient can run on (csrc/gemm.hip's wgrad_plan / wgrad_group_plan), as patterns for has():
+# the two row-range head kernels, the split-K tile engine alone (VWgradOp) and in a group (VWgradGroupOp), the one
+# bf16x6 product, and the kernel that sums the slabs of a single job / of a group.
+DENSE_WGRAD_KERNELS = (r"\bwgrad_tr_kernel\b", r"\bwgrad_direct_kernel\b", r"\bvgemm_kernel<[^,]*\bVWgradOp\b",
+                       r"\bvgemm_kernel<[^,]*\bVWgradGroupOp\b", r"\bbgemm_kernel\b", r"\bslab_reduce_kernel\b",
+                       r"\bslab_reduce_group_kernel\b")
