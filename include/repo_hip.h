@@ -33,7 +33,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-#define REPO_ABI_VERSION 9
+#define REPO_ABI_VERSION 10
 
 #define REPO_OK 0
 #define REPO_E_BADARG (-1)
@@ -555,6 +555,39 @@ int repo_normal_entropy(int64_t n, const float* std, float gscale, float* dstd, 
 int repo_lambda_return(int64_t Hm, int64_t N, const float* rewards, const float* values, float gamma,
                        float lambda_, float gret, float* returns, float* drewards, float* dvalues,
                        float* ret_sum, void* ws, size_t ws_bytes, hipStream_t stream);
+
+/* ------------------------------------------------------------------ inverse-dynamics auxiliary (ABI v10)
+ * config.inv_dynamics: InverseDynamicsModel (models/utils.py:84-109) trained on DETACHED latents after every
+ * world-model step (Dreamer.train_inv_dynamics, dreamer.py:220-239; called from dreamer.py:300 and repo.py:110).  Its
+ * dense chain is repo_mlp_fwd_act / repo_mlp_bwd_act with (in_dim, hidden, out_dim) = (2D+S, hidden, 2A), 4 layers; the
+ * two entry points below are what stands before and behind it (csrc/invdyn.hip). */
+/* The model's input, torch.cat((beliefs[:-1], states[:-1], beliefs[1:]), dim=1) over flattened (time, batch)
+ * (dreamer.py:222-230 with models/utils.py:103): featx points at the observe scan's T x B rows [belief (D) | state (S)]
+ * (row pitch ldfeat >= D+S) and x (N, 2D+S), N = (T-1)*B, row pitch ldx, receives
+ *   x[t*B + b] = [featx[t][b][0:D+S] | featx[t+1][b][0:D]]     for t < T-1.
+ * A pure copy (bit-exact) that writes every element of the N x (2D+S) block; any D, S >= 1 -- 16-byte and 8-byte accesses
+ * are used only where every row segment keeps that alignment, single floats otherwise.  Rows whose transition is masked
+ * out are packed too: the selection (nonterm_inds, dreamer.py:221) is repo_normal_nll_rows's mask. */
+int repo_inv_dyn_pack(int64_t T, int64_t B, int64_t D, int64_t S, const float* featx, int64_t ldfeat, float* x,
+                      int64_t ldx, hipStream_t stream);
+/* -Independent(Normal(mean, std), 1).log_prob(target).mean() over the SELECTED rows (dreamer.py:221,232-233) of a head
+ * whose output is raw (N, 2A), row pitch ldraw: mean = raw[:, :A], std = softplus(raw[:, A:]) + min_std (torch.chunk and
+ * F.softplus -- linear above 20 -- at models/utils.py:107-108).  target (N, A), row pitch ldt; row r is selected iff
+ * mask[r] == 1.0f (nonterms[1:-1].flatten() == 1).
+ *   sums[0] = sum over the selected rows of sum_j (0.5 z^2 + log std + 0.5 log 2 pi), z = (target - mean) / std
+ *   sums[1] = the number of selected rows
+ *   draw (nullable; (N, 2A), row pitch lddraw) = d(sums[0] / count) / d raw with count = *count_in (a DEVICE float, e.g.
+ *          the all-reduced sums[1] of a data-parallel job) or, count_in NULL, the kernel's own sums[1] -- formed in the
+ *          same launch.  Unselected rows receive exact zeros (written, not skipped).
+ * count == 0: sums = {0, 0} and draw is all zeros; nothing is NaN (the reference's mean over zero rows is NaN and its
+ * Adam step then writes NaN into the module).  One launch; fixed summation order, no floating-point atomics: two calls
+ * give identical bits.  N <= 2^20 (REPO_E_SHAPE above): the one-launch form is meant for an update's rows -- thousands;
+ * every block of the launch reads the whole mask once for the divisor.  ws: repo_normal_nll_rows_workspace_bytes() of scratch whose first word is zero on entry
+ * and left zero (the header convention of repo_reduce_workspace_bytes(), whose buffer is large enough and may be shared). */
+size_t repo_normal_nll_rows_workspace_bytes(void);
+int repo_normal_nll_rows(int64_t N, int64_t A, const float* raw, int64_t ldraw, const float* target, int64_t ldt,
+                         const float* mask, const float* count_in, float min_std, float* sums, float* draw,
+                         int64_t lddraw, void* ws, size_t ws_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------ multitask (task-conditioned) agents
  * MultitaskDreamer / MultitaskRePo (algorithms/repo/dreamer_mt.py, repo_mt.py) condition every module on the task

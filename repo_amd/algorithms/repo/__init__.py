@@ -1,8 +1,10 @@
 from .dreamer import Dreamer
 from .dreamer_mt import MultitaskDreamer
+from .models.utils import InverseDynamicsModel
 from .repo import RePo
 from .repo_adapt import FinetunedRePo
 from .repo_mt import MultitaskRePo
 from .tia import TIA
 
-__all__ = ["Dreamer", "RePo", "TIA", "FinetunedRePo", "MultitaskDreamer", "MultitaskRePo"]
+__all__ = ["Dreamer", "RePo", "TIA", "FinetunedRePo", "MultitaskDreamer", "MultitaskRePo",
+           "InverseDynamicsModel"]

@@ -32,7 +32,7 @@ from .models.actor_critic import ActorModel, ValueModel
 from .models.decoder import ObservationModel, RewardModel
 from .models.encoder import Encoder
 from .models.rssm import TransitionModel
-from .models.utils import FlatAdam
+from .models.utils import FlatAdam, InverseDynamicsModel
 from .rollout import EpisodeDriver
 
 LOG_2PI = math.log(2.0 * math.pi)
@@ -129,17 +129,34 @@ class Dreamer:
         self._restore_point = None
 
     # ------------------------------------------------------------------ construction
+    # config.inv_dynamics: Dreamer, RePo (and FinetunedRePo, which builds and checkpoints the module but never trains it,
+    # like the reference's train_encoder).  TIA and the multitask agents have their own train_dynamics, from which the
+    # reference never trains the module (tia.py, dreamer_mt.py, repo_mt.py): they refuse the switch.
+    _BUILDS_INV_DYNAMICS = True
+
     def build_models(self, config, env):
         if not config.pixel_obs:
             raise NotImplementedError("only pixel observations are on the MI355X hot path")
-        if getattr(config, "disag_model", False) or getattr(config, "inv_dynamics", False):
-            raise NotImplementedError("disagreement / inverse-dynamics auxiliaries are out of scope (SURVEY 2.1 #10)")
+        if getattr(config, "disag_model", False):
+            raise NotImplementedError("disag_model=True: the latent-disagreement ensemble is not built (SURVEY 2.1 #10)")
+        self._inv_dyn = bool(getattr(config, "inv_dynamics", False))
+        if self._inv_dyn and not self._BUILDS_INV_DYNAMICS:
+            raise NotImplementedError(
+                f"inv_dynamics=True: {type(self).__name__} never trains the inverse-dynamics model (neither does the "
+                "reference's); the auxiliary is built for Dreamer, RePo and FinetunedRePo")
         obs_size = env.observation_space.shape
         action_size = int(np.prod(env.action_space.shape))
         self.action_size = action_size
         self._npix = int(np.prod(obs_size))  # 3*64*64 (the reference's frames) or 3*128*128 (build-defined)
         self._build_modules(config, env, obs_size, action_size)
         self._build_optimizers(config)
+        if self._inv_dyn:
+            # behind the value model, as the reference constructs it (dreamer.py:130-141) => same default init under a seed
+            self.inv_dynamics = InverseDynamicsModel(
+                config.belief_size, config.state_size, action_size, config.inv_dynamics_hidden_size,
+                config.dense_activation_function,
+            ).to(self.device)
+            self.inv_dynamics_optimizer = FlatAdam(self.inv_dynamics.parameters(), lr=config.inv_dynamics_lr)
 
     def _build_modules(self, config, env, obs_size, action_size):
         """The six modules (the multitask agents build the task-conditioned ones instead: dreamer_mt.py)."""
@@ -419,8 +436,50 @@ class Dreamer:
         self._model_step()
         self._pending_model = (torch.cat([st["nll_sum"], st["rew_sums"], kl_sum, self.model_optimizer.sqnorm]), None,
                                grow)
-        D = c.belief_size
-        return sv.featx[1:, :, :D], sv.featx[1:, :, D:]
+        return self._latents_out(sv, actions, nonterms)
+
+    def _latents_out(self, sv, actions, nonterms):
+        """The tail of every train_dynamics: the detached (beliefs, posterior_states) views of the scan's output, behind
+        the inverse-dynamics step if the agent has one (dreamer.py:300-302, repo.py:110-112)."""
+        D = self.c.belief_size
+        beliefs, states = sv.featx[1:, :, :D], sv.featx[1:, :, D:]
+        if self._inv_dyn:
+            self.train_inv_dynamics(beliefs, states, actions, nonterms)
+        return beliefs, states
+
+    # ------------------------------------------------------------------ inverse dynamics
+    def train_inv_dynamics(self, beliefs, states, actions, nonterms):
+        """One step of the inverse-dynamics auxiliary (reference dreamer.py:220-239): the action between consecutive
+        latents as a Normal, NLL over the transitions with nonterms[1:-1] == 1, its own clip and Adam.  beliefs (T,B,D),
+        states (T,B,S): the scan's output (detached by construction: nothing here reaches the world model); actions
+        (L,B,A), nonterms (L,B,1) with L = T + 1.  pack -> mlp_fwd -> NLL -> mlp_bwd -> clip_and_step, in line on the
+        current stream behind the model step: it reads the forward scan's output and its own parameters only.  The row
+        count is data dependent and stays on the device (repo_normal_nll_rows); with no selected row the gradient is zero,
+        the Adam step runs on it and the logged loss is nan (the reference would write NaN into the module)."""
+        c = self.c
+        m, opt = self.inv_dynamics, self.inv_dynamics_optimizer
+        T, B, D = beliefs.shape
+        S = states.shape[2]
+        rows = beliefs.as_strided((T, B, D + S), beliefs.stride()) if (
+            states.data_ptr() == beliefs.data_ptr() + 4 * D and states.stride() == beliefs.stride()
+            and beliefs.stride(1) >= D + S) else torch.cat((beliefs, states), dim=2)
+        x = ops.inv_dyn_pack(rows, D)
+        N = x.shape[0]
+        p, g = self._pg(m)
+        raw, hid = ops.mlp_fwd(p, x, act=m.act)
+        target, mask = actions[1:-1].reshape(N, -1), nonterms[1:-1].reshape(N)
+        if self.dp is None:
+            sums, draw = ops.normal_nll_rows(raw, target, mask, m.min_std_dev)
+        else:
+            # the mean is over the GLOBAL selection: count first, exchange it, then the gradient with that divisor
+            sums, _ = ops.normal_nll_rows(raw, target, mask, m.min_std_dev, want_grad=False)
+            total = sums.clone()   # `sums` stays this rank's partial sums for the (summed) scalar log
+            self._allreduce(total)
+            _, draw = ops.normal_nll_rows(raw, target, mask, m.min_std_dev, count_in=total[1:2])
+        ops.mlp_bwd(p, x, hid, draw, dparams=g, dx=None, act=m.act)
+        self._allreduce(opt.grad)
+        opt.clip_and_step(c.grad_clip_norm)
+        self._pending_extra = (sums, opt.sqnorm.clone())
 
     # ------------------------------------------------------------------ actor critic
     def train_actor_critic(self, beliefs, posterior_states, cond=None):
@@ -558,6 +617,9 @@ class Dreamer:
             dual.record_stream(cur)
         # a sibling algorithm's own loss sums / gradient norms (TIA): behind the shared ones of each kind
         xs, xn = self._pending_extra if self._pending_extra is not None else (msc[:0], msc[:0])
+        if self._pending_extra is not None:
+            xs.record_stream(cur)
+            xn.record_stream(cur)
         self._pending_extra = None
         parts = [msc[:4], ret_sum, ent_sum, lat_sum, v_sums, xs, msc[4:5], self.actor_optimizer.sqnorm,
                  self.value_optimizer.sqnorm, xn]
@@ -628,6 +690,10 @@ class Dreamer:
         self._last_scalars = out
         self.last_grad_norms = {"model": math.sqrt(max(gm, 0.0)), "actor": math.sqrt(max(ga_, 0.0)),
                                 "value": math.sqrt(max(gv_, 0.0))}
+        if self._inv_dyn and xsums:   # train_inv_dynamics: [NLL sum, selected rows], squared pre-clip gradient norm
+            nll_i, count_i = xsums
+            out["train/inv_dyn_loss"] = nll_i / count_i if count_i > 0 else float("nan")
+            self.last_grad_norms["inv_dynamics"] = math.sqrt(max(xnorms[0], 0.0))
         for k, v in out.items():
             self.logger.record(k, v)
         return None
@@ -848,7 +914,7 @@ class Dreamer:
         def sd(m):
             return {k: v.detach().clone() for k, v in m.state_dict().items()}
 
-        return {
+        params = {
             "step": self.step,
             "encoder": sd(self.encoder),
             "transition_model": sd(self.transition_model),
@@ -860,6 +926,10 @@ class Dreamer:
             "actor_optimizer": self.actor_optimizer.state_dict(),
             "value_optimizer": self.value_optimizer.state_dict(),
         }
+        if self._inv_dyn:   # dreamer.py:517-519
+            params["inv_dynamics"] = sd(self.inv_dynamics)
+            params["inv_dynamics_optimizer"] = self.inv_dynamics_optimizer.state_dict()
+        return params
 
     def load_checkpoint(self, ckpt_dir=None):
         if ckpt_dir is None:
@@ -891,6 +961,9 @@ class Dreamer:
         self.model_optimizer.load_state_dict(params["model_optimizer"])
         self.actor_optimizer.load_state_dict(params["actor_optimizer"])
         self.value_optimizer.load_state_dict(params["value_optimizer"])
+        if self._inv_dyn and "inv_dynamics" in params:   # a checkpoint without them loads (dreamer.py:560-564)
+            self._load_module(self.inv_dynamics, params["inv_dynamics"])
+            self.inv_dynamics_optimizer.load_state_dict(params["inv_dynamics_optimizer"])
         # the checkpoint keeps the reference's key layout (no noise state in it): resume behind every normal the
         # saved run can have drawn, instead of replaying the first updates' noise at offset 0
         self._noise_counter = max(self._noise_counter, self.model_optimizer.step_count * self._noise_stride())

@@ -1,6 +1,7 @@
-"""bottle + the flat-buffer Adam that replaces torch.optim.Adam / clip_grad_norm_.
+"""bottle, the inverse-dynamics model + the flat-buffer Adam that replaces torch.optim.Adam / clip_grad_norm_.
 
 bottle: /root/reference/algorithms/repo/models/utils.py:9-16.
+InverseDynamicsModel: /root/reference/algorithms/repo/models/utils.py:84-109.
 FlatAdam: the reference builds Adam(list_of_params, lr) (dreamer.py:96,106,114; repo.py:23) and
 calls zero_grad / clip_grad_norm_ / step (repo.py:87-90).  Here all parameters of a group live
 in ONE contiguous device buffer (each nn.Parameter is a view into it, as is its .grad), so the
@@ -9,6 +10,8 @@ data-parallel all-reduce is one collective.  state_dict()/load_state_dict() keep
 torch.optim.Adam's layout so reference checkpoints round-trip.
 """
 import torch
+import torch.nn as nn
+import torch.nn.functional as F
 
 from .... import ops
 
@@ -20,6 +23,31 @@ def bottle(f, xs):
     if isinstance(ys, tuple):
         return tuple(y.reshape(horizon, batch_size, *y.shape[1:]) for y in ys)
     return ys.reshape(horizon, batch_size, *ys.shape[1:])
+
+
+class InverseDynamicsModel(nn.Module):
+    """(2 belief + state) -> hidden^3 -> 2 action MLP on cat([belief, state, next_belief]): the action that led from
+    one latent to the next, as a Normal (mean, softplus + min_std_dev).  activation_function "elu" or "relu" (the
+    reference's default argument), `self.act` its REPO_ACT_* id.  Trained by Dreamer.train_inv_dynamics."""
+
+    def __init__(self, belief_size, state_size, action_size, hidden_size, activation_function="relu", min_std_dev=0.1):
+        super().__init__()
+        self.act = ops.dense_act_id(activation_function, type(self).__name__)
+        self.min_std_dev = min_std_dev
+        self.fc1 = nn.Linear(belief_size + state_size + belief_size, hidden_size)
+        self.fc2 = nn.Linear(hidden_size, hidden_size)
+        self.fc3 = nn.Linear(hidden_size, hidden_size)
+        self.fc4 = nn.Linear(hidden_size, 2 * action_size)
+
+    def plist(self):
+        return [t for m in (self.fc1, self.fc2, self.fc3, self.fc4) for t in (m.weight, m.bias)]
+
+    @torch.no_grad()
+    def forward(self, belief, state, next_belief):
+        x = torch.cat((belief, state, next_belief), dim=1).float().contiguous()
+        raw, _ = ops.mlp_fwd([t.detach() for t in self.plist()], x, act=self.act)
+        mean, std_dev = torch.chunk(raw, chunks=2, dim=1)
+        return mean, F.softplus(std_dev) + self.min_std_dev
 
 
 def adam_param_group(lr, betas, eps, n_params):

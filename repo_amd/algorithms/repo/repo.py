@@ -115,7 +115,7 @@ class RePo(Dreamer):
                       betas=bo.betas, eps=bo.eps, out=self._dual_out, skip=self._ustatus)
         self._pending_model = (torch.cat([nll_sum, rew_sums, kl_sum, self.model_optimizer.sqnorm]), self._dual_out.clone(),
                                grow)
-        return sv.featx[1:, :, :D], sv.featx[1:, :, D:]
+        return self._latents_out(sv, actions, nonterms)
 
     def train_dynamics(self, obs, actions, rewards, nonterms):
         c = self.c
@@ -143,8 +143,7 @@ class RePo(Dreamer):
                       betas=bo.betas, eps=bo.eps, out=self._dual_out, skip=self._ustatus)
         self._pending_model = (torch.cat([st["nll_sum"], st["rew_sums"], kl_sum, self.model_optimizer.sqnorm]),
                                self._dual_out.clone(), grow)
-        D = c.belief_size
-        return sv.featx[1:, :, :D], sv.featx[1:, :, D:]
+        return self._latents_out(sv, actions, nonterms)
 
     def get_param_dict(self):
         params = super().get_param_dict()

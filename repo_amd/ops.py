@@ -811,6 +811,43 @@ def scalar_nll(pred, target, mask, scale, want_grad=True, out=None):
     return out, dpred
 
 
+def inv_dyn_pack(featx, D, out=None):
+    """The inverse-dynamics model's input rows (include/repo_hip.h, repo_inv_dyn_pack): featx (T, B, D+S) = the observe
+    scan's [belief (D) | state] rows (sv.featx[1:], or a column view of a wider buffer: rows contiguous, steps B rows
+    apart) -> x ((T-1)*B, 2D+S) = [belief_t | state_t | belief_t+1]."""
+    T, B, F = featx.shape
+    S = F - int(D)
+    ld = featx.stride(1)
+    assert featx.dtype == torch.float32 and featx.stride(2) == 1 and ld >= F and (T == 1 or featx.stride(0) == B * ld), (
+        featx.shape, featx.stride())
+    if out is None:
+        out = torch.empty((T - 1) * B, F + int(D), dtype=torch.float32, device=featx.device)
+    check(lib().repo_inv_dyn_pack(T, B, int(D), S, _ptr(featx), ld, _ptr(out), _ld(out), _stream()), "repo_inv_dyn_pack")
+    return out
+
+
+def normal_nll_rows(raw, target, mask, min_std=0.1, count_in=None, want_grad=True, out=None):
+    """Masked Normal NLL of a [mean | pre-softplus std] head over the rows with mask == 1 (include/repo_hip.h,
+    repo_normal_nll_rows): raw (N, 2A) and target (N, A) views with contiguous rows, mask (N,).  Returns (sums =
+    [NLL sum over the selected rows, selected rows], draw = the gradient of the MEAN loss w.r.t. raw, or None);
+    count_in: a device float that replaces the kernel's own count as the gradient's divisor (data parallel)."""
+    N, A2 = raw.shape
+    A = A2 // 2
+    dev = raw.device
+    assert A2 == 2 * A and tuple(target.shape) == (N, A) and mask.numel() == N, (raw.shape, target.shape, mask.shape)
+    draw = torch.empty(N, A2, dtype=torch.float32, device=dev) if want_grad else None
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = reduce_ws(dev, lib().repo_normal_nll_rows_workspace_bytes())
+    check(
+        lib().repo_normal_nll_rows(N, A, _ptr(raw), _ld(raw), _ptr(target), _ld(target), _ptr(_f32c(mask)),
+                                   _ptr(count_in), float(min_std), _ptr(out), _ptr(draw), 2 * A if want_grad else 0,
+                                   _ptr(ws), ws.numel(), _stream()),
+        "repo_normal_nll_rows",
+    )
+    return out, draw
+
+
 def tia_blend_nll(t_out, d_out, mask_wb, target, grad_scale, want_grads=True, want_recon=False, inplace=False):
     """TIA's masked blend of the task / distractor decoder outputs + pixel NLL (tia.py:123-133).
     t_out, d_out (n,6,H,W); mask_wb (7,) = mask_head weight(6) + bias; target (n,3,H,W) uint8 | float32.
