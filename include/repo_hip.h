@@ -33,7 +33,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-#define REPO_ABI_VERSION 10
+#define REPO_ABI_VERSION 11
 
 #define REPO_OK 0
 #define REPO_E_BADARG (-1)
@@ -588,6 +588,36 @@ size_t repo_normal_nll_rows_workspace_bytes(void);
 int repo_normal_nll_rows(int64_t N, int64_t A, const float* raw, int64_t ldraw, const float* target, int64_t ldt,
                          const float* mask, const float* count_in, float min_std, float* sums, float* draw,
                          int64_t lddraw, void* ws, size_t ws_bytes, hipStream_t stream);
+
+/* ------------------------------------------------------------------ state-vector observations (ABI v11)
+ * config.pixel_obs = False: SymbolicEncoder / SymbolicObservationModel (models/encoder.py, models/decoder.py) are three
+ * Linear layers each with the activation after the first two -- repo_mlp_fwd_act / repo_mlp_bwd_act chains.  The entry
+ * point below is the decoder's ending in training (csrc/symbolic.hip): the last Linear fused with the observation loss
+ * -Normal(pred, 1).log_prob(target).sum(dim=2) (dreamer.py:262-267), as repo_decoder_out_nll is for pixels.
+ *   h (rows, K) pitch ldh, W (O, K) pitch ldw, bias (O), target (rows, O) pitch ldt:  pred = h W^T + bias
+ *   sums[0]              = sum over rows and outputs of 0.5 (pred - target)^2   (the constant 0.5 log(2 pi) O per row is
+ *                          the host's, added where the scalar is logged)
+ *   dpre (rows, O), pitch lddpre = (pred - target) * grad_scale
+ *   recon (nullable; rows, O), pitch ldrecon = pred
+ * Every element of the (rows, O) blocks of dpre and recon is written; pitches may exceed the widths (column views of
+ * wider buffers).  rows >= 1, 1 <= O <= 1024, K >= 1 (REPO_E_SHAPE otherwise, and beyond the 32-bit extents of repo_gemm).
+ * fp32 throughout (fp32 MFMA accumulation); fixed summation order, no floating-point atomics: two calls give identical
+ * bits.  The backward of the layer (dW, db, dh) is repo_mlp_bwd_act on dpre with this layer as the chain's last.
+ * One fused launch (plus a one-block sum when the grid exceeds 64 workgroups) when K, ldh and ldw are multiples of 4, h
+ * and W are 16-byte aligned and the grid has at most 2048 workgroups of 32 rows x 64 outputs; otherwise the entry point
+ * composes repo_gemm with an NLL pass over the pitched block: it then needs somewhere to put pred -- recon, or `scratch`
+ * (rows * O floats; REPO_E_WS_TOO_SMALL without either).  repo_linear_unit_nll_fused() tells which form a call takes (1 =
+ * fused), so a caller allocates scratch only when needed.  ws: repo_reduce_workspace_bytes() of scratch under the header
+ * convention stated there (first word zero on entry, left zero). */
+int repo_linear_unit_nll_fused(int64_t rows, int64_t O, int64_t K, const float* h, int64_t ldh, const float* W,
+                               int64_t ldw);
+int repo_linear_unit_nll(int64_t rows, int64_t O, int64_t K, const float* h, int64_t ldh, const float* W, int64_t ldw,
+                         const float* bias, const float* target, int64_t ldt, float grad_scale, float* sums, float* dpre,
+                         int64_t lddpre, float* recon, int64_t ldrecon, float* scratch, size_t scratch_bytes, void* ws,
+                         size_t ws_bytes, hipStream_t stream);
+/* Test / measurement aid, thread-local like the switches above: 0 = the dispatch (default), 1 = the fused kernel wherever
+ * its operands allow it, 2 = the composition everywhere; returns the calling thread's previous setting. */
+int repo_debug_linear_nll(int mode);
 
 /* ------------------------------------------------------------------ multitask (task-conditioned) agents
  * MultitaskDreamer / MultitaskRePo (algorithms/repo/dreamer_mt.py, repo_mt.py) condition every module on the task

@@ -81,6 +81,11 @@ def mlp_apply(mod, belief, state):
     return _MlpFn.apply(feat, getattr(mod, "act", ops.ACT_ELU), *mod.plist())
 
 
+def dense_apply(mod, x):
+    """A dense chain on its own input rows (SymbolicEncoder: no [belief | state] concatenation)."""
+    return _MlpFn.apply(x.contiguous(), mod.act, *mod.plist())
+
+
 class _ObserveFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prev_belief, prev_state, actions, embeds, nonterms, eps_prior, eps_post, min_std, act, *params):

@@ -133,10 +133,16 @@ class Dreamer:
     # like the reference's train_encoder).  TIA and the multitask agents have their own train_dynamics, from which the
     # reference never trains the module (tia.py, dreamer_mt.py, repo_mt.py): they refuse the switch.
     _BUILDS_INV_DYNAMICS = True
+    # config.pixel_obs = False (state-vector observations: SymbolicEncoder / SymbolicObservationModel):
+    # Dreamer and RePo.  FinetunedRePo, TIA and the multitask agents have encoders / decoders of their own: they refuse.
+    _BUILDS_SYMBOLIC = True
 
     def build_models(self, config, env):
-        if not config.pixel_obs:
-            raise NotImplementedError("only pixel observations are on the MI355X hot path")
+        self._symbolic = not config.pixel_obs
+        if self._symbolic and not self._BUILDS_SYMBOLIC:
+            raise NotImplementedError(
+                f"pixel_obs=False: {type(self).__name__} is built for pixel observations only; state-vector observations "
+                "are built for Dreamer and RePo")
         if getattr(config, "disag_model", False):
             raise NotImplementedError("disag_model=True: the latent-disagreement ensemble is not built (SURVEY 2.1 #10)")
         self._inv_dyn = bool(getattr(config, "inv_dynamics", False))
@@ -148,6 +154,8 @@ class Dreamer:
         action_size = int(np.prod(env.action_space.shape))
         self.action_size = action_size
         self._npix = int(np.prod(obs_size))  # 3*64*64 (the reference's frames) or 3*128*128 (build-defined)
+        if self._symbolic:   # a flat state vector (dreamer.py:53-54): its length is the modules' size and the NLL's constant
+            obs_size = self._npix = int(env.observation_space.shape[0])
         self._build_modules(config, env, obs_size, action_size)
         self._build_optimizers(config)
         if self._inv_dyn:
@@ -162,13 +170,13 @@ class Dreamer:
         """The six modules (the multitask agents build the task-conditioned ones instead: dreamer_mt.py)."""
         dev = self.device
         # same construction order as the reference (dreamer.py:57-114) => same default init under a seed
-        self.encoder = Encoder(False, obs_size, config.embedding_size, config.cnn_activation_function).to(dev)
+        self.encoder = Encoder(self._symbolic, obs_size, config.embedding_size, config.cnn_activation_function).to(dev)
         self.transition_model = TransitionModel(
             config.belief_size, config.state_size, action_size, config.hidden_size, config.embedding_size,
             config.dense_activation_function,
         ).to(dev)
         self.obs_model = ObservationModel(
-            False, obs_size, config.belief_size, config.state_size, config.embedding_size,
+            self._symbolic, obs_size, config.belief_size, config.state_size, config.embedding_size,
             config.cnn_activation_function,
         ).to(dev)
         self.reward_model = RewardModel(
@@ -293,13 +301,16 @@ class Dreamer:
         frames = obs[1:].reshape(rows, *obs.shape[2:])
         st["frames"] = frames
         pe, _ = self._pg(self.encoder)
-        embeds, st["enc_saved"] = Fn.encoder_fwd(pe, frames)
+        if self._symbolic:
+            embeds, st["enc_saved"] = Fn.symbolic_encoder_fwd(pe, frames, self.encoder.act)
+        else:
+            embeds, st["enc_saved"] = Fn.encoder_fwd(pe, frames)
         pr, _ = self._pg(self.transition_model)
         b0, s0 = self._zero_state(B)
         pd, _ = self._pg(self.obs_model)
         # the decoder's composed first layers (functional.dec_head_compose) depend on the parameters only: made here, under
         # the latency-bound scan, off the decoder's chain
-        head = Fn.dec_head_compose(pd) if Fn._dec_compose(rows) else None
+        head = Fn.dec_head_compose(pd) if not self._symbolic and Fn._dec_compose(rows) else None
         sv = ops.rssm_observe_fwd(
             pr, b0, s0, actions[:-1].contiguous(), nonterms[:-1].reshape(T, B).contiguous(), embeds.view(T, B, -1),
             self._noise("obs_prior", (T, B, S)), self._noise("obs_post", (T, B, S)), self.transition_model.min_std_dev,
@@ -312,7 +323,10 @@ class Dreamer:
         feat = sv.featx[1:].reshape(rows, D + S)
         st["feat"] = feat
         # decoder + pixel NLL (mean over (T,B) of the per-frame sums)
-        st["nll_sum"], st["dec_saved"] = Fn.decoder_fwd_nll(pd, feat, frames, 1.0 / grow, head=head)
+        if self._symbolic:   # the three dense layers, the last one fused with the NLL summed over the vector
+            st["nll_sum"], st["dec_saved"] = Fn.symbolic_decoder_fwd_nll(pd, feat, frames, 1.0 / grow, self.obs_model.act)
+        else:
+            st["nll_sum"], st["dec_saved"] = Fn.decoder_fwd_nll(pd, feat, frames, 1.0 / grow, head=head)
         # reward head; predicted from the next state, masked by nonterminal (repo.py:58-61)
         pw, _ = self._pg(self.reward_model)
         r_pred, st["rew_hid"] = ops.mlp_fwd(pw, feat, act=self.reward_model.act)
@@ -336,6 +350,17 @@ class Dreamer:
         pe, ge = self._pg(self.encoder)
         dembeds = torch.empty(rows, self.c.embedding_size, device=dev)
         dpm, dps, dqm, dqs = kl_grads
+        if self._symbolic:
+            # state vectors: two dense chains around the reverse scan, in line on one stream (no weight-gradient side
+            # stream; an update is the scan, the imagination and dense chains only).  Dreamer's decoder is attached, so its
+            # input gradient accumulates into dfeat ahead of the scan; RePo's is a probe on detached latents.
+            Fn.symbolic_decoder_bwd(pd, feat, st["dec_saved"], gd, self.obs_model.act,
+                                    dfeat=dfeat if decoder_attached else None, accumulate_dfeat=True)
+            self._model_bucket_begin(tail=True)   # decoder + reward-head gradients are final
+            ops.rssm_observe_bwd(pr, sv, gr, dfeat=dfeat, dpm=dpm, dps=dps, dqm=dqm, dqs=dqs, dembeds=dembeds,
+                                 min_std=self.transition_model.min_std_dev)
+            Fn.symbolic_encoder_bwd(pe, st["frames"], st["enc_saved"], dembeds, ge, self.encoder.act)
+            return
         if decoder_attached:
             # Dreamer: the decoder's INPUT gradient feeds the reverse scan, so the data-gradient chain runs
             # first; the decoder's weight gradients feed nothing downstream and are issued afterwards,
@@ -423,7 +448,8 @@ class Dreamer:
 
     def train_dynamics(self, obs, actions, rewards, nonterms):
         """Dreamer world-model step (reference dreamer.py:241-302).  obs (L,B,3,64,64) float32 in
-        [-1,1] (reference convention) or uint8; returns detached (beliefs, posterior_states)."""
+        [-1,1] (reference convention) or uint8 -- pixel_obs=False: (L,B,obs_size) float32; returns detached (beliefs,
+        posterior_states)."""
         c = self.c
         obs, actions, rewards, nonterms = self._prep_batch(obs, actions, rewards, nonterms)
         st = self._world_model_forward(obs, actions, rewards, nonterms)

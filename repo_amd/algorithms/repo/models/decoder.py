@@ -1,5 +1,5 @@
-"""Transposed-conv observation model and reward head
-(reference: algorithms/repo/models/decoder.py:28-48,178-195)."""
+"""Transposed-conv observation model, state-vector observation model and reward head
+(reference: algorithms/repo/models/decoder.py:6-48,178-195)."""
 import torch.nn as nn
 
 
@@ -65,9 +65,36 @@ class TIAObservationModel(nn.Module):
         return decoder_apply(self, belief, state).chunk(2, 1)
 
 
+class SymbolicObservationModel(nn.Module):
+    """cat([belief, state]) -> fc1 -> act -> fc2 -> act -> fc3 -> (n, obs) (reference models/decoder.py:6-25).  Children
+    hold parameters only; training ends in repo_linear_unit_nll (repo_amd.functional.symbolic_decoder_*).  Same children,
+    shapes and construction order as the reference.  activation_function "relu" or "elu"
+    (config.cnn_activation_function), `self.act` its REPO_ACT_* id."""
+
+    def __init__(self, observation_size, belief_size, state_size, embedding_size, activation_function="relu"):
+        super().__init__()
+        from .... import ops
+        from .encoder import check_observation_size
+
+        self.act = ops.dense_act_id(activation_function, type(self).__name__)
+        self.observation_size = check_observation_size(observation_size, type(self).__name__)
+        self.embedding_size = embedding_size
+        self.fc1 = nn.Linear(belief_size + state_size, embedding_size)
+        self.fc2 = nn.Linear(embedding_size, embedding_size)
+        self.fc3 = nn.Linear(embedding_size, self.observation_size)
+
+    def plist(self):
+        return [t for m in (self.fc1, self.fc2, self.fc3) for t in (m.weight, m.bias)]
+
+    def forward(self, belief, state):
+        from ..autograd import mlp_apply
+
+        return mlp_apply(self, belief, state)
+
+
 def ObservationModel(symbolic, observation_size, belief_size, state_size, embedding_size, activation_function="relu"):
     if symbolic:
-        raise NotImplementedError("symbolic (non-pixel) observations are outside the MI355X hot path")
+        return SymbolicObservationModel(observation_size, belief_size, state_size, embedding_size, activation_function)
     return VisualObservationModel(belief_size, state_size, embedding_size, activation_function,
                                   image_size=int(observation_size[-1]))
 

@@ -1,4 +1,4 @@
-"""Conv image encoder (reference: algorithms/repo/models/encoder.py:21-47)."""
+"""Conv image encoder and the state-vector encoder (reference: algorithms/repo/models/encoder.py:6-47)."""
 import torch
 import torch.nn as nn
 
@@ -44,7 +44,44 @@ class VisualEncoder(nn.Module):
         return encoder_apply(self, observation)
 
 
+MAX_OBSERVATION_SIZE = 1024   # state vectors of 1 .. 1024 floats (the contract of the symbolic modules)
+
+
+def check_observation_size(observation_size, what):
+    n = int(observation_size)
+    if not 1 <= n <= MAX_OBSERVATION_SIZE:
+        raise NotImplementedError(f"{what}: observation_size {n} is outside 1 .. {MAX_OBSERVATION_SIZE}, the widths the "
+                                  "state-vector (pixel_obs=False) modules are built and tested for")
+    return n
+
+
+class SymbolicEncoder(nn.Module):
+    """observation (n, obs) -> fc1 -> act -> fc2 -> act -> fc3 -> (n, embedding) (reference models/encoder.py:6-18): a
+    dense chain on repo_mlp_fwd_act / repo_mlp_bwd_act.  Same children, shapes and construction order as the reference,
+    hence the same default initialisation under a seed and the same state_dict.  activation_function "relu" or "elu"
+    (config.cnn_activation_function, as the reference passes it), `self.act` its REPO_ACT_* id."""
+
+    def __init__(self, observation_size, embedding_size, activation_function="relu"):
+        super().__init__()
+        from .... import ops
+
+        self.act = ops.dense_act_id(activation_function, type(self).__name__)
+        self.observation_size = check_observation_size(observation_size, type(self).__name__)
+        self.embedding_size = embedding_size
+        self.fc1 = nn.Linear(self.observation_size, embedding_size)
+        self.fc2 = nn.Linear(embedding_size, embedding_size)
+        self.fc3 = nn.Linear(embedding_size, embedding_size)
+
+    def plist(self):
+        return [t for m in (self.fc1, self.fc2, self.fc3) for t in (m.weight, m.bias)]
+
+    def forward(self, observation):
+        from ..autograd import dense_apply
+
+        return dense_apply(self, observation)
+
+
 def Encoder(symbolic, observation_size, embedding_size, activation_function="relu"):
     if symbolic:
-        raise NotImplementedError("symbolic (non-pixel) observations are outside the MI355X hot path")
+        return SymbolicEncoder(observation_size, embedding_size, activation_function)
     return VisualEncoder(embedding_size, activation_function, image_size=int(observation_size[-1]))

@@ -120,7 +120,8 @@ class RePo(Dreamer):
     def train_dynamics(self, obs, actions, rewards, nonterms):
         c = self.c
         obs, actions, rewards, nonterms = self._prep_batch(obs, actions, rewards, nonterms)
-        if os.environ.get("REPO_WM_SPLIT", "1") == "1" and self._side_stream is not None:
+        # (state vectors: no conv stacks to overlap -- the serial order below, one stream)
+        if os.environ.get("REPO_WM_SPLIT", "1") == "1" and self._side_stream is not None and not self._symbolic:
             return self._train_dynamics_split(obs, actions, rewards, nonterms)
         st = self._world_model_forward(obs, actions, rewards, nonterms)
         sv, grow = st["sv"], st["grow"]

@@ -21,6 +21,8 @@ from .repo import RePo
 
 
 class FinetunedRePo(RePo):
+    _BUILDS_SYMBOLIC = False   # pixel_obs=False: train_encoder runs the conv encoder's passes (the reference pins uint8 frames)
+
     def build_models(self, config, env):
         super().build_models(config, env)
         n_enc = len(list(self.encoder.parameters()))

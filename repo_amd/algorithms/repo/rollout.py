@@ -33,7 +33,10 @@ class EpisodeDriver:
     def advance(self):
         """Filter on the current observation, act, step the environment once."""
         seen = self.obs
-        frame = to_torch(preprocess(seen[None]), device=self.agent.device)
+        frame = preprocess(seen[None])
+        if frame.dtype != np.float32:   # a state vector as the environment gives it (float64): the modules take float32
+            frame = frame.astype(np.float32)
+        frame = to_torch(frame, device=self.agent.device)
         self.latent = self.agent.update_latent_and_select_action(*self.latent, frame, self.explore)
         action = to_np(self.latent[2])[0]
         if not np.isfinite(action).all():

@@ -1,6 +1,6 @@
 """Multi-kernel building blocks shared by the nn.Module wrappers and the agents' hand-scheduled
-update: conv encoder, transposed-conv decoder (+ fused pixel NLL) and their backward passes,
-expressed over repo_amd.ops (the C ABI).  Parameter lists are in the reference modules'
+update: conv encoder, transposed-conv decoder (+ fused pixel NLL), their state-vector counterparts and
+their backward passes, expressed over repo_amd.ops (the C ABI).  Parameter lists are in the reference modules'
 state_dict order; gradients are written in place into caller-provided tensors (views of the
 flat gradient buffer), so no autograd graph and no extra accumulation pass are involved.
 """
@@ -319,3 +319,42 @@ def _decoder_bwd_tail(p, feat, h0, h1, h2, d3, g, dfeat, accumulate_dfeat, accum
     if dfeat is not None:
         ops.gemm(dh0, p[0], out=dfeat, accumulate=accumulate_dfeat)
     fk.join()
+
+
+# ----------------------------------------------------------------------------- state-vector observations
+# config.pixel_obs = False: SymbolicEncoder / SymbolicObservationModel are three Linear layers each, the activation after
+# the first two.  The encoder is one dense chain (ops.mlp_fwd / ops.mlp_bwd); the decoder's first two layers are two
+# products with the activation in the epilogue and its last layer is fused with the observation NLL
+# (ops.linear_unit_nll), whose pre-activation gradient is the upstream of ONE ops.mlp_bwd over the three layers.  The
+# `saved` tuples take the places of the conv stacks' in the agents' update.
+_ACT_EPI = {ops.ACT_ELU: ops.EPI_ELU, ops.ACT_RELU: ops.EPI_RELU}
+
+
+def symbolic_encoder_fwd(p, obs, act):
+    """SymbolicEncoder.forward.  obs (n, obs_size) float32; p = [fc1.w, fc1.b, fc2.w, fc2.b, fc3.w, fc3.b].
+    Returns (embeds (n, E), saved = the two hidden activations)."""
+    embeds, hid = ops.mlp_fwd(p, obs, act=act)
+    return embeds, tuple(hid)
+
+
+def symbolic_encoder_bwd(p, obs, saved, dembeds, g, act, accumulate=False):
+    """Gradients of all six encoder tensors into g (same order as p)."""
+    ops.mlp_bwd(p, obs, list(saved), dembeds, dparams=g, accumulate_w=accumulate, dx=None, act=act)
+
+
+def symbolic_decoder_fwd_nll(p, feat, target, grad_scale, act, want_recon=False):
+    """SymbolicObservationModel.forward fused with the unit-variance NLL summed over the observation vector
+    (dreamer.py:262-267 with .sum(2)).  Returns (sum 0.5 (recon - target)^2 (1,), saved = (h1, h2, d loss / d fc3's
+    output * grad_scale, recon or None))."""
+    h1 = ops.linear(feat, p[0], p[1], epi=_ACT_EPI[act])
+    h2 = ops.linear(h1, p[2], p[3], epi=_ACT_EPI[act])
+    loss_sum, dpre, recon = ops.linear_unit_nll(h2, p[4], p[5], target, grad_scale, want_recon=want_recon)
+    return loss_sum, (h1, h2, dpre, recon)
+
+
+def symbolic_decoder_bwd(p, feat, saved, g, act, dfeat=None, accumulate_dfeat=False, accumulate=False):
+    """Backward from saved[2] (the output layer's pre-activation gradient) to all six decoder tensors (into g) and, if
+    dfeat is given (Dreamer's attached decoder), to the [belief|state] input."""
+    h1, h2, dpre = saved[:3]
+    ops.mlp_bwd(p, feat, [h1, h2], dpre, dparams=g, accumulate_w=accumulate, dx=dfeat, accumulate_dx=accumulate_dfeat,
+                act=act)

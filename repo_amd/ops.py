@@ -848,6 +848,37 @@ def normal_nll_rows(raw, target, mask, min_std=0.1, count_in=None, want_grad=Tru
     return out, draw
 
 
+def linear_unit_nll(h, w, b, target, grad_scale, want_recon=False, dpre=None, out=None):
+    """The symbolic decoder's output layer fused with the unit-variance Normal NLL (include/repo_hip.h,
+    repo_linear_unit_nll): h (rows, K), w (O, K), b (O,), target (rows, O) -- views with contiguous rows.  Returns
+    (sum of 0.5 (h w^T + b - target)^2 as a (1,) tensor, dpre = (pred - target) * grad_scale, recon or None).  `dpre`: an
+    optional (rows, O) view to write the gradient into.  One fused launch where K and the alignments allow 16-byte loads,
+    else repo_gemm + an NLL pass inside the entry point (it then gets scratch for the prediction unless recon is wanted)."""
+    rows, K = h.shape
+    O = w.shape[0]
+    dev = h.device
+    assert w.shape[1] == K and b.numel() == O and tuple(target.shape) == (rows, O), (h.shape, w.shape, b.shape, target.shape)
+    if dpre is None:
+        dpre = torch.empty(rows, O, dtype=torch.float32, device=dev)
+    assert tuple(dpre.shape) == (rows, O)
+    recon = torch.empty(rows, O, dtype=torch.float32, device=dev) if want_recon else None
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+    L = lib()
+    scratch, nscratch = None, 0
+    if recon is None and not L.repo_linear_unit_nll_fused(rows, O, K, _ptr(h), _ld(h), _ptr(w), _ld(w)):
+        nscratch = rows * O * 4
+        scratch = workspace(nscratch, dev)
+    ws = reduce_ws(dev)
+    check(
+        L.repo_linear_unit_nll(rows, O, K, _ptr(h), _ld(h), _ptr(w), _ld(w), _ptr(_f32c(b)), _ptr(target), _ld(target),
+                               float(grad_scale), _ptr(out), _ptr(dpre), _ld(dpre), _ptr(recon), O if want_recon else 0,
+                               _ptr(scratch), nscratch, _ptr(ws), ws.numel(), _stream()),
+        "repo_linear_unit_nll",
+    )
+    return out, dpre, recon
+
+
 def tia_blend_nll(t_out, d_out, mask_wb, target, grad_scale, want_grads=True, want_recon=False, inplace=False):
     """TIA's masked blend of the task / distractor decoder outputs + pixel NLL (tia.py:123-133).
     t_out, d_out (n,6,H,W); mask_wb (7,) = mask_head weight(6) + bias; target (n,3,H,W) uint8 | float32.
