@@ -33,7 +33,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-#define REPO_ABI_VERSION 11
+#define REPO_ABI_VERSION 12
 
 #define REPO_OK 0
 #define REPO_E_BADARG (-1)
@@ -66,6 +66,12 @@ typedef struct ihipStream_t* hipStream_t;
                                 Accepted by repo_conv_down, repo_conv_up (scatter kernels) and repo_gemm (c = n /
                                 bias_div, ldaux = 2 C): the modulation is an epilogue, the pre-FiLM tensor is never
                                 written; the backward pass recovers it from the output (repo_film_bwd_h)             */
+
+/* ABI v12 -- repo_gemm only: nn.LeakyReLU() (negative slope 0.01) of the VDB discriminator's dense chain
+ * (common/models/gans.py:70, mlps.py:11-32).  LeakyReLU preserves sign, so the saved output is its own slope mask.
+ * These are epilogues of repo_gemm, NOT a third REPO_ACT_*: the `_act` entry points still take {0, 1} only. */
+#define REPO_EPI_LEAKY 8      /* x > 0 ? x : 0.01 x                                      */
+#define REPO_EPI_MUL_DLEAKY 9 /* multiply by leaky'(x) (1 or 0.01) given aux = leaky(x)  */
 
 /* Dense activation (ABI v9): config.dense_activation_function of the reference, which builds every dense layer of the
  * RSSM (models/rssm.py:24, act_fn = getattr(F, activation_function)), the reward head (models/decoder.py:178-195) and
@@ -588,6 +594,69 @@ size_t repo_normal_nll_rows_workspace_bytes(void);
 int repo_normal_nll_rows(int64_t N, int64_t A, const float* raw, int64_t ldraw, const float* target, int64_t ldt,
                          const float* mask, const float* count_in, float min_std, float* sums, float* draw,
                          int64_t lddraw, void* ws, size_t ws_bytes, hipStream_t stream);
+
+/* ------------------------------------------------------------------ VDB discriminator (ABI v12)
+ * VDBDiscriminator (common/models/gans.py:56-156), the variational-bottleneck discriminator CalibratedRePo aligns its
+ * target encoder with (algorithms/repo/repo_adapt.py:400-482).  Its dense chain -- x (N, E) through n_hidden Linears with
+ * LeakyReLU(0.01), then a Linear to z = [mean (Z) | logstd (Z)] -- is repo_gemm with REPO_EPI_LEAKY / REPO_EPI_MUL_DLEAKY
+ * and repo_gemm_wgrad; the entry points below are what stands behind it (csrc/vdb.hip).  All fp32; every reduction has a
+ * fixed summation order and uses no floating-point atomics: two calls give identical bits.  eps (N, Z) contiguous, or
+ * NULL + (noise_seed, noise_offset): element n*Z + j is normal number noise_offset + n*Z + j (N*Z consumed); a backward
+ * call is given what its forward was given.  z, a5, dz are views with row pitch ld* >= 2Z; lat, extra, delta5 rows are
+ * contiguous.  N >= 1, Z >= 1, N * ld < 2^31 (REPO_E_SHAPE otherwise).  `ws` of head_fwd / loss / gp_norm is a reduction
+ * workspace (repo_reduce_workspace_bytes(): first word zero on entry, left zero); `ws` of head_bwd / gp_head is plain
+ * scratch of repo_vdb_colsum_workspace_bytes(Z) bytes.
+ *
+ * repo_vdb_head_fwd (gans.py:80-88, 152-156):
+ *   lat[n][j] = mean + eps * exp(logstd);  d[n] = fc_b[0] + sum_j fc_w[j] * leaky(lat[n][j])
+ *   *kl_sum (nullable) = sum_n ( sum_j (-logstd + 0.5 (exp(2 logstd) + mean^2)) - Z / 2 )   (_compute_kl_prior, summed) */
+int repo_vdb_head_fwd(int64_t N, int64_t Z, const float* z, int64_t ldz, const float* eps, uint64_t noise_seed,
+                      uint64_t noise_offset, const float* fc_w, const float* fc_b, float* lat, float* d, float* kl_sum,
+                      void* ws, size_t ws_bytes, hipStream_t stream);
+/* *loss_sum = sum_n f(d[n]);  dd[n] (nullable) = gscale * f'(d[n])  (gscale: the 1/N of the mean times the loss's
+ * coefficient).  mode: */
+#define REPO_VDB_BCE0 0    /* binary_cross_entropy_with_logits(d, 0) = softplus(d)       (JS fake, gans.py:104)          */
+#define REPO_VDB_BCE1 1    /* binary_cross_entropy_with_logits(d, 1) = softplus(-d)      (JS real :97; generator side)   */
+#define REPO_VDB_NEG_TAU 2 /* -(tau[n] * d)   (support-mode real, gans.py:99; tau (N) required, a constant)             */
+#define REPO_VDB_CHI 3     /* d + d^2 / 4     (support-mode fake, gans.py:106)                                          */
+#define REPO_VDB_NEG_CHI 4 /* -(d + d^2 / 4)  (support-mode generator, repo_adapt.py:441)                               */
+int repo_vdb_loss(int64_t N, const float* d, int mode, const float* tau, float gscale, float* dd, float* loss_sum,
+                  void* ws, size_t ws_bytes, hipStream_t stream);
+/* The head's reverse pass, from dd = dL/dd (N) and the KL term  (*beta) * kl_coef * kl_row  (beta: a DEVICE scalar,
+ * nullable = no KL term; kl_coef = 0.5 / N_set for gans.py:109-113) and `extra` (nullable, (N, Z)): one more upstream on
+ * the logstd half (the gradient penalty's, repo_vdb_gp_head):
+ *   dlat = dd[n] fc_w[j] leaky'(lat);  dz[n][j] = dlat + c mean;  dz[n][Z+j] = dlat eps exp(logstd) + c (exp(2 logstd) - 1) + extra
+ *   dfc_w[j] (+)= sum_n dd[n] leaky(lat[n][j]);  dfc_b[0] (+)= sum_n dd[n]      (c = *beta * kl_coef)
+ * dfc_w / dfc_b nullable together (a frozen discriminator: only dz is wanted). */
+size_t repo_vdb_colsum_workspace_bytes(int64_t Z);
+int repo_vdb_head_bwd(int64_t N, int64_t Z, const float* z, int64_t ldz, const float* eps, uint64_t noise_seed,
+                      uint64_t noise_offset, const float* lat, const float* fc_w, const float* dd, const float* beta,
+                      float kl_coef, const float* extra, float* dz, int64_t lddz, float* dfc_w, float* dfc_b,
+                      int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
+/* *beta = max(*beta + beta_lr * (0.5 (kl_real_sum / n_real + kl_fake_sum / n_fake) - target_kl), 0)  (gans.py:111-127);
+ * kl_out (nullable) = the 0.5 (...) mean.  One launch, no host synchronisation. */
+int repo_vdb_beta_step(float* beta, const float* kl_real_sum, int64_t n_real, const float* kl_fake_sum, int64_t n_fake,
+                       float beta_lr, float target_kl, float* kl_out, hipStream_t stream);
+/* The zero-centred gradient penalty (gans.py:143-150), P = gp_weight / N * sum_n |g_n|^2 with g = d(sum d)/dx.
+ * repo_vdb_gp_delta: the upstream of that input-gradient chain at the chain's output,
+ *   delta5[n] = [r | r eps exp(logstd)],  r[j] = fc_w[j] leaky'(lat[n][j])        ((N, 2Z), row pitch lddelta). */
+int repo_vdb_gp_delta(int64_t N, int64_t Z, const float* z, int64_t ldz, const float* eps, uint64_t noise_seed,
+                      uint64_t noise_offset, const float* lat, const float* fc_w, float* delta5, int64_t lddelta,
+                      hipStream_t stream);
+/* *sq_sum = sum g^2 over n contiguous floats, then g *= scale (in place): the penalty's value (times gp_weight / N on the
+ * host side of the copy) and the upstream of its adjoint chain, ghat = 2 gp_weight g / N, in one pass. */
+int repo_vdb_gp_norm(int64_t n, float* g, float scale, float* sq_sum, void* ws, size_t ws_bytes, hipStream_t stream);
+/* The head end of the penalty's adjoint chain, from a5 = dP/d delta5 (N, 2Z):
+ *   dfc_w[j] (+)= sum_n (a5[n][j] + a5[n][Z+j] eps exp(logstd)) leaky'(lat[n][j])
+ *   extra[n][j] = a5[n][Z+j] fc_w[j] leaky'(lat[n][j]) eps exp(logstd)         (repo_vdb_head_bwd's `extra`) */
+int repo_vdb_gp_head(int64_t N, int64_t Z, const float* a5, int64_t lda5, const float* z, int64_t ldz, const float* eps,
+                     uint64_t noise_seed, uint64_t noise_offset, const float* lat, const float* fc_w, float* extra,
+                     float* dfc_w, int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
+/* The density-ratio losses of support mode (repo_adapt.py:465-476) on lt = log_tau(src) (N): tau = exp(lt),
+ *   sums[0] = sum tau d,  sums[1] = sum (tau - 1);  dlt[n] = tau (d[n] + *u) / N   (d, u constants).
+ * tau_out (nullable, (N)) = tau.  d NULL: only tau_out and sums[1] are formed (the tau handed to the discriminator). */
+int repo_vdb_tau(int64_t N, const float* lt, const float* d, const float* u, float* tau_out, float* dlt, float* sums,
+                 void* ws, size_t ws_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------ state-vector observations (ABI v11)
  * config.pixel_obs = False: SymbolicEncoder / SymbolicObservationModel (models/encoder.py, models/decoder.py) are three

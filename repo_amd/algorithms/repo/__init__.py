@@ -2,9 +2,9 @@ from .dreamer import Dreamer
 from .dreamer_mt import MultitaskDreamer
 from .models.utils import InverseDynamicsModel
 from .repo import RePo
-from .repo_adapt import FinetunedRePo
+from .repo_adapt import CalibratedRePo, FinetunedRePo
 from .repo_mt import MultitaskRePo
 from .tia import TIA
 
-__all__ = ["Dreamer", "RePo", "TIA", "FinetunedRePo", "MultitaskDreamer", "MultitaskRePo",
+__all__ = ["Dreamer", "RePo", "TIA", "FinetunedRePo", "CalibratedRePo", "MultitaskDreamer", "MultitaskRePo",
            "InverseDynamicsModel"]

@@ -311,6 +311,24 @@ class SequenceReplayBuffer:
         return d
 
 
+class CalibrationBuffer(SequenceReplayBuffer):
+    """The reference's paired ring of CalibratedRePo (/root/reference/algorithms/repo/repo_adapt.py:129-133): the
+    calibration environment's frames carry the source view in channels [0, C/2) and the target view in [C/2, C); every
+    batch comes back split along the channel axis: sample() -> (src_obs, tgt_obs, act, rew, done).  The ring, the pinned
+    staging path and the HBM mirror hold the paired frames whole; the device batch is split into two contiguous tensors
+    (the encoder's first convolution reads whole frames)."""
+
+    def _get_samples(self, batch_inds):
+        obs, act, rew, done = super()._get_samples(batch_inds)
+        src_obs, tgt_obs = np.split(obs, 2, axis=1)
+        return src_obs, tgt_obs, act, rew, done
+
+    def acquire(self, handle, batch_size, seq_len, device):
+        obs, act, rew, done = super().acquire(handle, batch_size, seq_len, device)
+        half = obs.shape[2] // 2
+        return obs[:, :, :half].contiguous(), obs[:, :, half:].contiguous(), act, rew, done
+
+
 class MultitaskSequenceReplayBuffer(SequenceReplayBuffer):
     """The reference's multitask ring (/root/reference/common/buffers.py:205-225): a `tasks` array (capacity,
     num_tasks) beside the four rings, `push(task, obs, act, rew, done)`, and every batch led by its task one-hots:

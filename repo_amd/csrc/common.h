@@ -62,6 +62,9 @@ __device__ __forceinline__ float act_grad_from_out(float h) {
 inline bool act_ok(int act) { return act == REPO_ACT_ELU || act == REPO_ACT_RELU; }
 inline int act_epi(int act) { return act == REPO_ACT_RELU ? REPO_EPI_RELU : REPO_EPI_ELU; }
 inline int act_epi_mul_d(int act) { return act == REPO_ACT_RELU ? REPO_EPI_MUL_DRELU : REPO_EPI_MUL_DELU; }
+// nn.LeakyReLU()'s default negative slope (the VDB discriminator, csrc/vdb.hip).  It preserves sign, so the saved OUTPUT is
+// its own slope mask: h > 0 <=> x > 0.
+constexpr float kLeakySlope = 0.01f;
 // torch F.softplus(beta=1, threshold=20)
 __device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : __logf(1.f + __expf(x)); }
 __device__ __forceinline__ float sigmoidf(float x) { return rcp_fast(1.f + __expf(-x)); }

@@ -26,6 +26,8 @@ struct DenseEpi {
     else if (epi == REPO_EPI_RELU) v = fmaxf(v, 0.f);
     else if (epi == REPO_EPI_MUL_DELU) v *= elu_grad_from_out(COL ? ax[dm * ldaux] : ax[(size_t)m * ldaux + n]);
     else if (epi == REPO_EPI_MUL_DRELU) v = (COL ? ax[dm * ldaux] : ax[(size_t)m * ldaux + n]) > 0.f ? v : 0.f;
+    else if (epi == REPO_EPI_LEAKY) v = v > 0.f ? v : kLeakySlope * v;
+    else if (epi == REPO_EPI_MUL_DLEAKY) v = (COL ? ax[dm * ldaux] : ax[(size_t)m * ldaux + n]) > 0.f ? v : kLeakySlope * v;
     else if (FILM && epi == REPO_EPI_FILM_RELU) {   // row m's FiLM table: [scale (C) | shift (C)], C = ldaux / 2, channel n / |bias_div|
       const int ch = bias_div == 1 ? n : n / (bias_div < 0 ? -bias_div : bias_div);
       const float* tb = aux + (size_t)m * ldaux;

@@ -490,8 +490,10 @@ extern "C" int repo_gemm(int transa, int transb, int64_t M, int64_t N, int64_t K
   REPO_REQUIRE(M >= 0 && N >= 0 && K >= 0, REPO_E_SHAPE);
   if (M == 0 || N == 0) return REPO_OK;
   REPO_REQUIRE(A && B && C, REPO_E_BADARG);
-  REPO_REQUIRE((epi >= REPO_EPI_NONE && epi <= REPO_EPI_MUL_DRELU) || epi == REPO_EPI_FILM_RELU, REPO_E_BADARG);
-  REPO_REQUIRE((epi != REPO_EPI_MUL_DELU && epi != REPO_EPI_MUL_DRELU && epi != REPO_EPI_FILM_RELU) || aux, REPO_E_BADARG);
+  REPO_REQUIRE((epi >= REPO_EPI_NONE && epi <= REPO_EPI_MUL_DRELU) || (epi >= REPO_EPI_FILM_RELU && epi <= REPO_EPI_MUL_DLEAKY),
+               REPO_E_BADARG);
+  REPO_REQUIRE((epi != REPO_EPI_MUL_DELU && epi != REPO_EPI_MUL_DRELU && epi != REPO_EPI_FILM_RELU && epi != REPO_EPI_MUL_DLEAKY) || aux,
+               REPO_E_BADARG);
   // FiLM: one table row per output row, [scale | shift] over the N / bias_div channels; not on the <= 8-row vector path
   {
     const int64_t fd = bias_div < 0 ? -bias_div : (bias_div > 0 ? bias_div : 1);   // pixels per FiLM channel

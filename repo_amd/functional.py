@@ -358,3 +358,35 @@ def symbolic_decoder_bwd(p, feat, saved, g, act, dfeat=None, accumulate_dfeat=Fa
     h1, h2, dpre = saved[:3]
     ops.mlp_bwd(p, feat, [h1, h2], dpre, dparams=g, accumulate_w=accumulate, dx=dfeat, accumulate_dx=accumulate_dfeat,
                 act=act)
+
+
+# ----------------------------------------------------------------------------- LeakyReLU dense chain (VDB discriminator)
+def leaky_chain_fwd(params, x):
+    """params [w1, b1, ..., wL, bL]: L Linears, nn.LeakyReLU(0.01) after all but the last (reference common/models/mlps.py
+    with act="LeakyReLU"), layer by layer on ops.gemm.  -> (out (N, out_dim), [the L-1 hidden activations])."""
+    L = len(params) // 2
+    h, hid = x, []
+    for l in range(L):
+        last = l == L - 1
+        h = ops.gemm(h, params[2 * l], transb=True, bias=params[2 * l + 1], epi=ops.EPI_NONE if last else ops.EPI_LEAKY)
+        if not last:
+            hid.append(h)
+    return h, hid
+
+
+def leaky_chain_bwd(params, x, hid, dout, dparams=None, accumulate=False, dx=None, accumulate_dx=False, keep=None):
+    """The reverse chain of leaky_chain_fwd: dparams (same layout as params; None = frozen weights) receive (+)= the weight
+    and bias gradients, dx (N, in_dim; None = detached input) the input gradient.  keep: a list that receives the
+    pre-activation gradients [of layer L, ..., of layer 1] -- the gradient penalty's adjoint chain needs them."""
+    L = len(params) // 2
+    dy = dout
+    for l in range(L - 1, -1, -1):
+        if keep is not None:
+            keep.append(dy)
+        if dparams is not None:
+            ops.gemm_wgrad(dy, hid[l - 1] if l else x, dW=dparams[2 * l], db=dparams[2 * l + 1], accumulate=accumulate)
+        if l:
+            dy = ops.gemm(dy, params[2 * l], epi=ops.EPI_MUL_DLEAKY, aux=hid[l - 1])
+        elif dx is not None:
+            ops.gemm(dy, params[0], out=dx, accumulate=accumulate_dx)
+    return dx

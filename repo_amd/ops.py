@@ -14,6 +14,7 @@ import torch
 from ._lib import check, lib
 
 EPI_NONE, EPI_ELU, EPI_RELU, EPI_MUL_DELU, EPI_MUL_DRELU, EPI_MUL_MASK4, EPI_MUL_CMASK, EPI_FILM_RELU = 0, 1, 2, 3, 4, 5, 6, 7
+EPI_LEAKY, EPI_MUL_DLEAKY = 8, 9   # nn.LeakyReLU(0.01) of the VDB discriminator's chain: repo_gemm only, not a REPO_ACT_*
 # dense activation of the RSSM / MLP-head kernels (REPO_ACT_*, include/repo_hip.h): config.dense_activation_function
 ACT_ELU, ACT_RELU = 0, 1
 DENSE_ACTIVATIONS = {"elu": ACT_ELU, "relu": ACT_RELU}
@@ -1092,3 +1093,108 @@ def dual_step_tasks(log_beta, exp_avg, exp_avg_sq, sums, rows, lr, betas, eps, s
                                      float(betas[0]), float(betas[1]), float(eps), int(step), int(bool(apply)), _ptr(out),
                                      _ptr(skip), _stream()), "repo_dual_step_tasks")
     return out
+
+
+# ----------------------------------------------------------------------------- VDB discriminator (csrc/vdb.hip)
+VDB_BCE0, VDB_BCE1, VDB_NEG_TAU, VDB_CHI, VDB_NEG_CHI = range(5)
+
+
+def _eps_args(eps, noise):
+    """(pointer, seed, offset) of a noise operand: an explicit contiguous tensor, or None + the Philox (seed, offset)."""
+    if eps is not None:
+        return _ptr(_f32c(eps)), 0, 0
+    return None, int(noise[0]), int(noise[1])
+
+
+def vdb_head_fwd(z, fc_w, fc_b, eps=None, noise=(0, 0), want_kl=True):
+    """z (N, 2Z) = [mean | logstd] -> (lat (N, Z), d (N,), kl_sum (1,) or None): include/repo_hip.h, repo_vdb_head_fwd."""
+    N, Z = z.shape[0], z.shape[1] // 2
+    dev = z.device
+    lat = torch.empty(N, Z, dtype=torch.float32, device=dev)
+    d = torch.empty(N, dtype=torch.float32, device=dev)
+    kl = torch.empty(1, dtype=torch.float32, device=dev) if want_kl else None
+    ws = reduce_ws(dev)
+    ep, seed, off = _eps_args(eps, noise)
+    check(lib().repo_vdb_head_fwd(N, Z, _ptr(z), _ld(z), ep, seed, off, _ptr(_f32c(fc_w)), _ptr(fc_b), _ptr(lat), _ptr(d),
+                                  _ptr(kl), _ptr(ws), ws.numel(), _stream()), "repo_vdb_head_fwd")
+    return lat, d, kl
+
+
+def vdb_loss(d, mode, gscale=0.0, tau=None, want_grad=True, out=None):
+    """-> (loss_sum (1,), dd (N,) = gscale * f'(d) or None) for one of the VDB_* losses (repo_vdb_loss)."""
+    N = d.numel()
+    dev = d.device
+    dd = torch.empty(N, dtype=torch.float32, device=dev) if want_grad else None
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = reduce_ws(dev)
+    check(lib().repo_vdb_loss(N, _ptr(_f32c(d)), int(mode), _ptr(tau), float(gscale), _ptr(dd), _ptr(out), _ptr(ws),
+                              ws.numel(), _stream()), "repo_vdb_loss")
+    return out, dd
+
+
+def vdb_head_bwd(z, lat, fc_w, dd, eps=None, noise=(0, 0), beta=None, kl_coef=0.0, extra=None, dfc_w=None, dfc_b=None,
+                 accumulate=False):
+    """-> dz (N, 2Z); dfc_w (Z,) / dfc_b (1,) are written (or accumulated into) when given (repo_vdb_head_bwd)."""
+    N, Z = z.shape[0], z.shape[1] // 2
+    dev = z.device
+    dz = torch.empty(N, 2 * Z, dtype=torch.float32, device=dev)
+    nb = lib().repo_vdb_colsum_workspace_bytes(Z)
+    ws = workspace(nb, dev)
+    ep, seed, off = _eps_args(eps, noise)
+    check(lib().repo_vdb_head_bwd(N, Z, _ptr(z), _ld(z), ep, seed, off, _ptr(_f32c(lat)), _ptr(_f32c(fc_w)), _ptr(_f32c(dd)),
+                                  _ptr(beta), float(kl_coef), _ptr(extra), _ptr(dz), 2 * Z, _ptr(dfc_w), _ptr(dfc_b),
+                                  int(accumulate), _ptr(ws), ws.numel(), _stream()), "repo_vdb_head_bwd")
+    return dz
+
+
+def vdb_beta_step(beta, kl_real, n_real, kl_fake, n_fake, beta_lr, target_kl, kl_out=None):
+    check(lib().repo_vdb_beta_step(_ptr(beta), _ptr(kl_real), int(n_real), _ptr(kl_fake), int(n_fake), float(beta_lr),
+                                   float(target_kl), _ptr(kl_out), _stream()), "repo_vdb_beta_step")
+
+
+def vdb_gp_delta(z, lat, fc_w, eps=None, noise=(0, 0)):
+    """-> delta5 (N, 2Z), the upstream of the gradient penalty's input-gradient chain (repo_vdb_gp_delta)."""
+    N, Z = z.shape[0], z.shape[1] // 2
+    out = torch.empty(N, 2 * Z, dtype=torch.float32, device=z.device)
+    ep, seed, off = _eps_args(eps, noise)
+    check(lib().repo_vdb_gp_delta(N, Z, _ptr(z), _ld(z), ep, seed, off, _ptr(_f32c(lat)), _ptr(_f32c(fc_w)), _ptr(out),
+                                  2 * Z, _stream()), "repo_vdb_gp_delta")
+    return out
+
+
+def vdb_gp_norm(g, scale, out=None):
+    """-> sum g^2 (1,); g *= scale in place (repo_vdb_gp_norm)."""
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=g.device)
+    ws = reduce_ws(g.device)
+    check(lib().repo_vdb_gp_norm(g.numel(), _ptr(_f32c(g)), float(scale), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+          "repo_vdb_gp_norm")
+    return out
+
+
+def vdb_gp_head(a5, z, lat, fc_w, dfc_w, eps=None, noise=(0, 0), accumulate=False):
+    """-> extra (N, Z), the penalty's upstream on the logstd half; dfc_w (+)= its fc.weight gradient (repo_vdb_gp_head)."""
+    N, Z = z.shape[0], z.shape[1] // 2
+    dev = z.device
+    extra = torch.empty(N, Z, dtype=torch.float32, device=dev)
+    ws = workspace(lib().repo_vdb_colsum_workspace_bytes(Z), dev)
+    ep, seed, off = _eps_args(eps, noise)
+    check(lib().repo_vdb_gp_head(N, Z, _ptr(a5), _ld(a5), _ptr(z), _ld(z), ep, seed, off, _ptr(_f32c(lat)),
+                                 _ptr(_f32c(fc_w)), _ptr(extra), _ptr(dfc_w), int(accumulate), _ptr(ws), ws.numel(),
+                                 _stream()), "repo_vdb_gp_head")
+    return extra
+
+
+def vdb_tau(lt, d=None, u=None, want_tau=False, want_grad=False, out=None):
+    """lt (N,) = log_tau(src) -> (sums (2,) = [sum tau d, sum (tau - 1)], tau or None, dlt or None) (repo_vdb_tau)."""
+    N = lt.numel()
+    dev = lt.device
+    tau = torch.empty(N, dtype=torch.float32, device=dev) if want_tau else None
+    dlt = torch.empty(N, dtype=torch.float32, device=dev) if want_grad else None
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = reduce_ws(dev)
+    check(lib().repo_vdb_tau(N, _ptr(_f32c(lt)), _ptr(d), _ptr(u), _ptr(tau), _ptr(dlt), _ptr(out), _ptr(ws), ws.numel(),
+                             _stream()), "repo_vdb_tau")
+    return out, tau, dlt

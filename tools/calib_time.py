@@ -1,0 +1,117 @@
+"""What one CalibratedRePo.simple_pair_calibration step costs at the bench shapes (B = L = 50, A = 6, the reference's
+discriminator widths 256 / 64), and what the discriminator adds to it: the step as it is, and the same step with every
+discriminator call stubbed out (the four encoder forwards, the calibration NLL, the two encoder backwards and the Adam
+step remain; the alignment gradient is a constant tensor).  Three rings mirrored in HBM, a fresh batch every step, 5 warm-up
++ 20 timed steps; each measurement runs in a fresh child process, alternating.
+usage: python tools/calib_time.py                      js, js-stub, support, support-stub, twice, then the discriminator's kernels
+       python tools/calib_time.py MODE [stub]          one measurement in this process (MODE: js | support)
+       python tools/calib_time.py kernels MODE         device time of every kernel of one VDBDiscriminator.train call"""
+import os, subprocess, sys, time
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, HERE)
+
+
+def make_agent(mode):
+    import numpy as np
+    import bench
+    from repo_amd.algorithms.repo import CalibratedRePo
+    cfg = bench.config("repo")
+    for k, v in dict(inv_dynamics=True, inv_dynamics_lr=3e-4, inv_dynamics_hidden_size=512, calibration_mode="simple_pair",
+                     alignment_mode=mode, calibration_buffer_size=5000, expert_calib_data=True, calib_time_limit=500,
+                     aln_coef=1.0, dyn_coef=1.0, calib_coef=1.0, f_lr=3e-4, f_latent_size=64, f_target_kl=0.1,
+                     f_hidden_size=256, tau_lr=5e-5, u_lr=5e-3, init_u=1e-4, source_dir="", offline_truncate_size=1000000,
+                     replay_size=5000).items():
+        setattr(cfg, k, v)
+
+    class PairedEnv(bench.Env):
+        def __init__(self):
+            super().__init__()
+            self.observation_space = bench.Space((6, 64, 64))
+
+    agent = CalibratedRePo(cfg, bench.Env(), bench.Env(), PairedEnv(), bench.NullLogger())
+    rs = np.random.RandomState(0)
+    for buf in (agent.buffer, agent.src_buffer, agent.calib_buffer):
+        buf.observations[:] = rs.randint(0, 256, size=buf.observations.shape, dtype=np.uint8)
+        buf.pos, buf.full = 0, True
+        buf.invalidate_mirror()
+    return agent, cfg
+
+
+def stub_discriminator(agent):
+    """Every discriminator / density-ratio call of the step becomes a constant: what is left is the encoder's cost."""
+    import torch
+    from types import SimpleNamespace
+    from repo_amd import ops
+    c = agent.c
+    N, E = c.batch_size * c.chunk_size, c.embedding_size
+    dev = agent.device
+    const = SimpleNamespace(d=torch.zeros(N, device=dev), dx=torch.full((N, E), 1e-6, device=dev),
+                            buf=torch.zeros(5, device=dev), one=torch.zeros(1, device=dev))
+    disc = agent.disc
+    disc.train = lambda *a, **k: SimpleNamespace(buf=const.buf, scales=(1.0,) * 5)
+    disc.fwd = lambda x, **k: SimpleNamespace(d=const.d, x=x)
+    disc.input_grad = lambda sv, dd: const.dx
+    ops.vdb_loss = lambda d, mode, gscale=0.0, **k: (const.one, const.d)
+    ops.vdb_tau = lambda lt, **k: (torch.zeros(2, device=dev), const.d, const.d.clone())
+    agent.log_tau.fwd = lambda x: (const.d.view(N, 1), None)
+    agent.log_tau.bwd = lambda *a, **k: None
+
+
+def measure(mode, stub):
+    import torch
+    agent, cfg = make_agent(mode)
+    if stub:
+        stub_discriminator(agent)
+    cfg.train_steps = 5
+    agent.train_agent(); torch.cuda.synchronize()
+    cfg.train_steps = 20
+    t0 = time.perf_counter()
+    agent.train_agent(); torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    what = "discriminator stubbed out (encoder only)" if stub else "whole step"
+    print(f"alignment_mode={mode}, {what}: {dt/20*1e3:.3f} ms per simple_pair_calibration step incl. sampling"
+          + ("" if stub else f"; encoder_loss {agent.last_scalars['train/encoder_loss']:.4f}"), flush=True)
+
+
+def kernels(mode):
+    """Device time of every kernel of ONE VDBDiscriminator.train call on an idle device (mean of 10 calls)."""
+    import torch
+    from torch.profiler import ProfilerActivity, profile
+    agent, cfg = make_agent(mode)
+    N, E = cfg.batch_size * cfg.chunk_size, cfg.embedding_size
+    g = torch.Generator(device="cuda").manual_seed(0)
+    xr, xf = torch.randn(N, E, device="cuda", generator=g) * 0.1, torch.randn(N, E, device="cuda", generator=g) * 0.1
+    tau = torch.rand(N, device="cuda", generator=g) + 0.5 if mode == "support" else None
+    call = lambda: agent.disc.train(xr, xf, tau)  # noqa: E731
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    n = 10
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(n):
+            call()
+        torch.cuda.synchronize()
+    rows = {}
+    for e in prof.events():
+        if e.device_time_total > 0 and "Memcpy" not in e.name and "Memset" not in e.name:
+            c = rows.setdefault(e.name, [0, 0.0])
+            c[0] += 1
+            c[1] += e.device_time_total
+    total = sum(t for _, t in rows.values())
+    print(f"VDBDiscriminator.train ({mode}, N = {N}): {total / n:.1f} us of kernel time per call, "
+          f"{sum(c for c, _ in rows.values()) // n} launches")
+    for name, (c, t) in sorted(rows.items(), key=lambda kv: -kv[1][1])[:14]:
+        print(f"  {t / n:8.1f} us  x{c // n:<3d} {name[:150]}")
+
+
+if __name__ == "__main__":
+    me = os.path.abspath(__file__)
+    if len(sys.argv) > 2 and sys.argv[1] == "kernels":
+        kernels(sys.argv[2])
+    elif len(sys.argv) > 1 and sys.argv[1] in ("js", "support"):
+        measure(sys.argv[1], len(sys.argv) > 2 and sys.argv[2] == "stub")
+    else:
+        for _ in range(2):
+            for args in (["js"], ["js", "stub"], ["support"], ["support", "stub"]):
+                subprocess.run([sys.executable, me, *args], cwd=HERE, check=True, timeout=240)
+        subprocess.run([sys.executable, me, "kernels", "js"], cwd=HERE, check=True, timeout=240)
