@@ -33,7 +33,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-#define REPO_ABI_VERSION 12
+#define REPO_ABI_VERSION 13
 
 #define REPO_OK 0
 #define REPO_E_BADARG (-1)
@@ -367,6 +367,27 @@ int repo_rssm_observe_bwd_act(int64_t T, int64_t B, int64_t A, int64_t D, int64_
                               float* dprev_state, int accumulate, unsigned* status, void* ws, size_t ws_bytes,
                               hipStream_t stream, int act);
 
+/* ABI v13: the reverse scan for FROZEN transition weights (CalibratedRePo's calibration_mode="pair",
+ * algorithms/repo/repo_adapt.py:245-398: only the encoder trains).  The same scan kernels as repo_rssm_observe_bwd_act on
+ * both engines -- `engine` = 0 (the row scan) or 2 (the column-split engine, the value of `accumulate`'s bit 1) -- and
+ * d embeds = dhq W_bq[:, D:] behind them; none of the eight weight-gradient products runs and the workspace (a query of
+ * its own, never larger than repo_rssm_observe_bwd_workspace_bytes) carries no slab for one.  dembeds, dprev_belief and
+ * dprev_state (each nullable) equal those of repo_rssm_observe_bwd_act given the same arguments.  With dprior_state, dpm
+ * and dps all NULL the column-split engine's prior-head launches in front of the scan are skipped: they would hand the
+ * scan zeros. */
+size_t repo_rssm_observe_bwd_frozen_workspace_bytes(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd,
+                                                    int64_t S, int64_t E);
+int repo_rssm_observe_bwd_frozen(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t E,
+                                 const float* const* params, const float* nonterms, const float* embeds,
+                                 const float* eps_prior, const float* eps_post, uint64_t noise_seed,
+                                 uint64_t noise_offset, float min_std,
+                                 const float* featx, const float* prior_std, const float* post_std,
+                                 const float* xsa, const float* e, const float* gates, const float* hp,
+                                 const float* hq, const float* dfeat, const float* dprior_state,
+                                 const float* dpm, const float* dps, const float* dqm, const float* dqs,
+                                 float* dembeds, float* dprev_belief, float* dprev_state, int engine,
+                                 unsigned* status, void* ws, size_t ws_bytes, hipStream_t stream, int act);
+
 /* ------------------------------------------------------------------ MLP heads
  * n_layers nn.Linear layers, ELU between (the `_act` forms: ELU or ReLU), last layer linear (RewardModel / ValueModel:
  * 4 layers, out_dim 1, models/decoder.py:189-195, models/actor_critic.py:20-26; ActorModel
@@ -576,6 +597,22 @@ int repo_lambda_return(int64_t Hm, int64_t N, const float* rewards, const float*
  * out are packed too: the selection (nonterm_inds, dreamer.py:221) is repo_normal_nll_rows's mask. */
 int repo_inv_dyn_pack(int64_t T, int64_t B, int64_t D, int64_t S, const float* featx, int64_t ldfeat, float* x,
                       int64_t ldx, hipStream_t stream);
+/* ABI v13: the same rows from TWO (T, B, D+S) blocks, each with a row pitch (ld) and a time pitch (td >= B * ld) of its
+ * own -- e.g. column blocks featx[1:, c0:c0+B] of a (T+1, Bscan, D+S) scan output (repo_adapt.py:343-357):
+ *   x[t*B + b] = [cur[t][b][0:D+S] | next[t+1][b][0:D]]     for t < T-1.
+ * Bit-exact; vectorised under repo_inv_dyn_pack's rule with both bases (column offsets included) and all pitches. */
+int repo_inv_dyn_pack_pair(int64_t T, int64_t B, int64_t D, int64_t S, const float* cur, int64_t ldcur, int64_t tdcur,
+                           const float* next, int64_t ldnext, int64_t tdnext, float* x, int64_t ldx,
+                           hipStream_t stream);
+/* The adjoint of repo_inv_dyn_pack_pair in gather form: dx_* (N, 2D+S) row gradients, dfeat a (T, B, D+S) block (row
+ * pitch lddfeat, time pitch tddfeat) that receives, for EVERY element (zeros included; accumulate: is added to),
+ *   [c < D+S, t <= T-2, dx_cur != NULL]  scale_cur  * dx_cur[t*B + b][c]
+ * + [c < D,   t >= 1]                    scale_next * dx_next[(t-1)*B + b][D+S + c].
+ * dx_cur NULL = no current term (the block only ever served as `next`).  One thread per element, no atomics: each term
+ * one fp32 multiply, the sum one fp32 add, in that order; two calls give identical bits. */
+int repo_inv_dyn_unpack_pair(int64_t T, int64_t B, int64_t D, int64_t S, const float* dx_cur, int64_t lddx_cur,
+                             const float* dx_next, int64_t lddx_next, float scale_cur, float scale_next, float* dfeat,
+                             int64_t lddfeat, int64_t tddfeat, int accumulate, hipStream_t stream);
 /* -Independent(Normal(mean, std), 1).log_prob(target).mean() over the SELECTED rows (dreamer.py:221,232-233) of a head
  * whose output is raw (N, 2A), row pitch ldraw: mean = raw[:, :A], std = softplus(raw[:, A:]) + min_std (torch.chunk and
  * F.softplus -- linear above 20 -- at models/utils.py:107-108).  target (N, A), row pitch ldt; row r is selected iff

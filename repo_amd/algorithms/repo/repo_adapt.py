@@ -9,14 +9,20 @@ RePo.  Here: encoder forward, the observe scan, the reward head's input gradient
 its gradient into the embeddings; the frozen weights' gradients it also forms are discarded) and the encoder backward,
 all on the update's kernels; one Adam over the encoder's slice of the model buffer (`FlatAdam.view`).
 
-`CalibratedRePo` (repo_adapt.py:136-596), calibration_mode="simple_pair": the frozen source encoder embeds source-domain
-replay and the source half of paired calibration frames; the target encoder is trained so that a variational-bottleneck
-discriminator (common/models/gans.py, csrc/vdb.hip) cannot tell its embeddings of target replay from the source's
-(alignment_mode "js" -- anything but "support" -- or "support": the chi-squared form against a learned density ratio
-tau = exp(log_tau) with its dual variable u) and so that its embeddings of the target half of the paired frames match the
-source's (a unit-variance Normal NLL).  One plain Adam step (no clipping) on the encoder's slice of the model buffer.
-Not built, each raising NotImplementedError by name: calibration_mode="pair" (the 3 B-row frozen scan with the
-inverse-dynamics loss), disag_model, pixel_obs=False, a data-parallel job.  DESIGN.md 6h.
+`CalibratedRePo` (repo_adapt.py:136-596): the frozen source encoder embeds source-domain replay and the source half of
+paired calibration frames; the target encoder is trained so that a variational-bottleneck discriminator
+(common/models/gans.py, csrc/vdb.hip) cannot tell its embeddings of target replay from the source's (alignment_mode "js"
+-- anything but "support" -- or "support": the chi-squared form against a learned density ratio tau = exp(log_tau) with
+its dual variable u) and
+ * calibration_mode="simple_pair": so that its embeddings of the target half of the paired frames match the source's (a
+   unit-variance Normal NLL);
+ * calibration_mode="pair" (repo_adapt.py:245-398): through the FROZEN world model's latents -- the frozen
+   inverse-dynamics model must explain the target trajectories (dyn_loss) and the transitions from a source latent to the
+   paired target latent (calib_loss); the gradient reaches the encoder through a reverse scan that forms no weight
+   gradient (repo_rssm_observe_bwd_frozen).  DESIGN.md 6i.
+One plain Adam step (no clipping) on the encoder's slice of the model buffer.
+Not built, each raising NotImplementedError by name: disag_model (so "pair" runs the reference's inv_dynamics branch
+only), pixel_obs=False, a data-parallel job.  DESIGN.md 6h, 6i.
 """
 import glob
 import os
@@ -150,6 +156,7 @@ class FinetunedRePo(RePo):
 class CalibratedRePo(RePo):
     _BUILDS_SYMBOLIC = False   # pixel_obs=False: the calibration frames are paired pixel frames (uint8, 6 channels)
     _LOG_KEYS = ("f_loss_src", "f_loss_tgt", "f_kl", "aln_loss", "calib_loss", "encoder_loss")
+    _LOG_KEYS_PAIR = ("dyn_loss",)
     _LOG_KEYS_SUPPORT = ("tau_loss", "tau_mean", "u_value")
 
     def __init__(self, config, env, eval_env, calib_env, logger):
@@ -192,9 +199,12 @@ class CalibratedRePo(RePo):
         self._cal_host = torch.empty(20, dtype=torch.float32).pin_memory()
 
     def _noise_stride(self):
-        """The discriminator's passes of one calibration step draw up to 4 L B Z normals on top of an update's."""
+        """The discriminator's passes of one calibration step draw up to 4 L B Z normals on top of an update's; the
+        "pair" step's scans over its 3 B columns draw 2 T 3B S more."""
         c = self.c
         per_update = super()._noise_stride() + 4 * c.chunk_size * c.batch_size * c.f_latent_size
+        if c.calibration_mode == "pair":
+            per_update += 2 * (c.chunk_size - 1) * 3 * c.batch_size * self.transition_model.state_size
         return 1 << max(int(per_update) - 1, 1).bit_length()
 
     # ------------------------------------------------------------------ acting with the source encoder
@@ -263,23 +273,41 @@ class CalibratedRePo(RePo):
         if self.dp is not None:
             raise NotImplementedError("CalibratedRePo: a data-parallel calibration step is not built")
         c = self.c
-        support = c.alignment_mode == "support"
         L, B = aln_src_obs.shape[:2]
-        N, E, Z = L * B, c.embedding_size, c.f_latent_size
-
-        def frames(o):
-            assert o.dtype in (torch.uint8, torch.float32), o.dtype
-            return o.reshape(N, *o.shape[2:]).contiguous()
-
+        N, E = L * B, c.embedding_size
         ps, _ = self._pg(self.src_encoder)
         pe, ge = self._pg(self.encoder)
-        f_at, f_ct = frames(aln_tgt_obs), frames(cal_tgt_obs)
-        aln_src, _ = Fn.encoder_fwd(ps, frames(aln_src_obs))
+        f_at, f_ct = self._frames(aln_tgt_obs), self._frames(cal_tgt_obs)
+        aln_src, _ = Fn.encoder_fwd(ps, self._frames(aln_src_obs))
         aln_tgt, sv_at = Fn.encoder_fwd(pe, f_at)
-        cal_src, _ = Fn.encoder_fwd(ps, frames(cal_src_obs))
+        cal_src, _ = Fn.encoder_fwd(ps, self._frames(cal_src_obs))
         cal_tgt, sv_ct = Fn.encoder_fwd(pe, f_ct)
-        # alignment: tau BEFORE the discriminator's step, d_tgt AFTER it (the updated discriminator, a fresh draw)
-        tau = None
+        al = self._alignment(aln_src, aln_tgt)
+        # calibration: -Normal(cal_tgt, 1).log_prob(cal_src).mean() over all N E elements
+        cal_sums, d_cal = ops.scalar_nll(cal_tgt.view(-1), cal_src.view(-1), None, c.calib_coef / (N * E))
+        # the encoder: two batches into one gradient, a plain Adam step (repo_adapt.py:451-454: no clipping)
+        Fn.encoder_bwd(pe, f_at, sv_at, al["d_aln"], ge, accumulate=False)
+        Fn.encoder_bwd(pe, f_ct, sv_ct, d_cal.view(N, E), ge, accumulate=True)
+        eo = self.encoder_optimizer
+        ops.grad_sqnorm(eo.grad, out=eo.sqnorm)   # logged only
+        eo.step()
+        parts = [al["info"].buf, al["aln_sum"], cal_sums[:1], eo.sqnorm, ops.grad_sqnorm(self.disc.optimizer.grad)]
+        parts += self._support_tail(aln_src, al)
+        self._queue_cal_log(parts, al["info"].scales, N, E, None)
+
+    @staticmethod
+    def _frames(o):
+        assert o.dtype in (torch.uint8, torch.float32), o.dtype
+        return o.reshape(o.shape[0] * o.shape[1], *o.shape[2:]).contiguous()
+
+    def _alignment(self, aln_src, aln_tgt):
+        """The alignment half of both calibration modes on the (N, E) embeddings of source and target replay
+        (repo_adapt.py:296-313 = 426-443): tau BEFORE the discriminator's step, d_tgt AFTER it (the updated discriminator,
+        a fresh draw).  -> the discriminator's info, the loss sum and d_aln = aln_coef d aln_loss / d aln_tgt (N, E)."""
+        c = self.c
+        support = c.alignment_mode == "support"
+        N, Z = aln_src.shape[0], c.f_latent_size
+        tau = lt = lt_hid = None
         if support:
             lt, lt_hid = self.log_tau.fwd(aln_src)
             _, tau, _ = ops.vdb_tau(lt.view(-1), want_tau=True)
@@ -288,53 +316,177 @@ class CalibratedRePo(RePo):
         e_t, n_t = self._eps("disc_tgt", N, Z)
         sv = self.disc.fwd(aln_tgt, eps=e_t, noise=n_t, want_kl=False)
         aln_sum, dd = ops.vdb_loss(sv.d, ops.VDB_NEG_CHI if support else ops.VDB_BCE1, c.aln_coef / N)
-        d_aln = self.disc.input_grad(sv, dd)
-        # calibration: -Normal(cal_tgt, 1).log_prob(cal_src).mean() over all N E elements
-        cal_sums, d_cal = ops.scalar_nll(cal_tgt.view(-1), cal_src.view(-1), None, c.calib_coef / (N * E))
-        # the encoder: two batches into one gradient, a plain Adam step (repo_adapt.py:451-454: no clipping)
-        Fn.encoder_bwd(pe, f_at, sv_at, d_aln, ge, accumulate=False)
-        Fn.encoder_bwd(pe, f_ct, sv_ct, d_cal.view(N, E), ge, accumulate=True)
-        eo = self.encoder_optimizer
-        ops.grad_sqnorm(eo.grad, out=eo.sqnorm)   # logged only
-        eo.step()
-        parts = [info.buf, aln_sum, cal_sums[:1], eo.sqnorm, ops.grad_sqnorm(self.disc.optimizer.grad)]
-        if support:
-            # the density ratio (repo_adapt.py:463-478): a fourth pass on the source embeddings, then log_tau and u step
-            e_s, n_s = self._eps("disc_src", N, Z)
-            svs = self.disc.fwd(aln_src, eps=e_s, noise=n_s, want_kl=False)
-            tau_sums, _, dlt = ops.vdb_tau(lt.view(-1), d=svs.d, u=self.u.detach().view(1), want_grad=True)
-            to, uo = self.tau_optimizer, self.u_optimizer
-            self.log_tau.bwd(aln_src, lt_hid, dlt.view(N, 1), dparams=[p.grad for p in self.log_tau.plist()])
-            ops.grad_sqnorm(to.grad, out=to.sqnorm)
-            u_old = self.u.detach().view(1).clone()
-            to.step()
-            torch.mul(tau_sums[1:2], -1.0 / N, out=uo.grad[:1])   # d(-u mean(tau - 1)) / du
-            uo.step()
-            parts += [tau_sums, u_old, self.u.detach().view(1), to.sqnorm]
-        # logging: one asynchronous copy, read when first needed
+        return dict(info=info, aln_sum=aln_sum, d_aln=self.disc.input_grad(sv, dd), lt=lt, lt_hid=lt_hid)
+
+    def _support_tail(self, aln_src, al):
+        """Support mode, behind the encoder's step: the density ratio (repo_adapt.py:379-398 = 463-478) -- a fourth pass
+        on the source embeddings, then log_tau and u step.  -> its log parts (none in js mode)."""
+        if self.c.alignment_mode != "support":
+            return []
+        N, Z = aln_src.shape[0], self.c.f_latent_size
+        lt, lt_hid = al["lt"], al["lt_hid"]
+        e_s, n_s = self._eps("disc_src", N, Z)
+        svs = self.disc.fwd(aln_src, eps=e_s, noise=n_s, want_kl=False)
+        tau_sums, _, dlt = ops.vdb_tau(lt.view(-1), d=svs.d, u=self.u.detach().view(1), want_grad=True)
+        to, uo = self.tau_optimizer, self.u_optimizer
+        self.log_tau.bwd(aln_src, lt_hid, dlt.view(N, 1), dparams=[p.grad for p in self.log_tau.plist()])
+        ops.grad_sqnorm(to.grad, out=to.sqnorm)
+        u_old = self.u.detach().view(1).clone()
+        to.step()
+        torch.mul(tau_sums[1:2], -1.0 / N, out=uo.grad[:1])   # d(-u mean(tau - 1)) / du
+        uo.step()
+        return [tau_sums, u_old, self.u.detach().view(1), to.sqnorm]
+
+    def _queue_cal_log(self, parts, scales, N, E, pair):
+        """Logging: one asynchronous copy, read when first needed.  pair: None, or the "pair" step's restore point (its
+        parts then hold two (NLL sum, selected rows) pairs and end with the scans' status word)."""
         self._flush_cal_log()
         buf = torch.cat(parts)
         self._cal_host[: buf.numel()].copy_(buf, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
-        self._cal_log = (ev, info.scales, N, E, support)
+        self._cal_log = (ev, scales, N, E, self.c.alignment_mode == "support", pair, buf.numel())
+
+    def pair_calibration(self):
+        """repo_adapt.py:245-269.  The same three batches in the same order, with the actions and dones of the target
+        replay and of the paired ring."""
+        B, L, dev = self.c.batch_size, self.c.chunk_size, self.device
+        aln_src = self.src_buffer.sample_to_device(B, L, dev)[0]
+        aln_tgt, aln_act, _, aln_done = self.buffer.sample_to_device(B, L, dev)
+        cal_src, cal_tgt, cal_act, _, cal_done = self.calib_buffer.sample_to_device(B, L, dev)
+        self.pair_calibration_step(aln_src, aln_tgt, aln_act, 1.0 - aln_done.float(), cal_src, cal_tgt, cal_act,
+                                   1.0 - cal_done.float())
+
+    def pair_calibration_step(self, aln_src_obs, aln_tgt_obs, aln_actions, aln_nonterms, cal_src_obs, cal_tgt_obs,
+                              cal_actions, cal_nonterms):
+        """The arithmetic of pair_calibration (repo_adapt.py:271-398, the inv_dynamics branch) on device batches: four
+        (L, B, 3, 64, 64) frame batches, actions (L, B, A) and nonterms (L, B, 1) of the target replay and of the paired
+        ring.  The reference's one scan over the 3 B columns [cal_src | cal_tgt | aln_tgt] runs as two -- its rows are
+        independent: forward only over cal_src (no gradient path: frozen encoder, frozen filter), forward and the frozen
+        reverse over [cal_tgt | aln_tgt].  Noise, in order: cal_prior, cal_post (T, 3 B, S) in the reference's column
+        order, then the discriminator's draws as in calibration_step.  DESIGN.md 6i."""
+        if self.dp is not None:
+            raise NotImplementedError("CalibratedRePo: a data-parallel calibration step is not built")
+        if not self._inv_dyn:
+            raise NotImplementedError('calibration_mode="pair" is built on the inverse-dynamics model (inv_dynamics=True); '
+                                      "the disag_model ensemble is not built")
+        c = self.c
+        self._update_seq += 1
+        self._restore_point = (self._update_seq, self._noise_counter, [(o, o.step_count) for o in self._steppers()])
+        L, B = aln_src_obs.shape[:2]
+        N, E = L * B, c.embedding_size
+        assert L >= 3, "the inverse-dynamics rows need chunks of three frames at least"
+        aln_actions, cal_actions = aln_actions.float().contiguous(), cal_actions.float().contiguous()
+        aln_nonterms, cal_nonterms = aln_nonterms.float().reshape(L, B), cal_nonterms.float().reshape(L, B)
+        ps, _ = self._pg(self.src_encoder)
+        pe, ge = self._pg(self.encoder)
+        f_at, f_ct = self._frames(aln_tgt_obs), self._frames(cal_tgt_obs)
+        aln_src, _ = Fn.encoder_fwd(ps, self._frames(aln_src_obs))
+        aln_tgt, sv_at = Fn.encoder_fwd(pe, f_at)
+        cal_src, _ = Fn.encoder_fwd(ps, self._frames(cal_src_obs))
+        cal_tgt, sv_ct = Fn.encoder_fwd(pe, f_ct)
+        lat = self._latent_losses(cal_src.view(L, B, E), cal_tgt.view(L, B, E), aln_tgt.view(L, B, E), cal_actions,
+                                  cal_nonterms, aln_actions, aln_nonterms)
+        # the two forward scans and the reverse one are behind us on this stream: the encoder's step (and log_tau's and
+        # u's) skips on a fault.  The discriminator's optimiser and its beta live on self.disc and do step
+        self._take_status()
+        al = self._alignment(aln_src, aln_tgt)
+        # -- the encoder: aln_tgt takes the alignment gradient on all L frames and the scan's on frames 1..L-1, cal_tgt
+        # the scan's alone (frame 0: zeros)
+        d_at = al["d_aln"].view(L, B, E)
+        d_at[1:] += lat["d_aln_tgt"]
+        Fn.encoder_bwd(pe, f_at, sv_at, d_at.view(N, E), ge, accumulate=False)
+        Fn.encoder_bwd(pe, f_ct, sv_ct, lat["d_cal_tgt"].view(N, E), ge, accumulate=True)
+        eo = self.encoder_optimizer
+        ops.grad_sqnorm(eo.grad, out=eo.sqnorm)   # logged only
+        eo.step()
+        parts = [al["info"].buf, al["aln_sum"], lat["dyn_sums"], lat["cal_sums"], eo.sqnorm,
+                 ops.grad_sqnorm(self.disc.optimizer.grad)]
+        parts += self._support_tail(aln_src, al)
+        parts.append(self._ustatus.view(torch.float32))
+        self._queue_cal_log(parts, al["info"].scales, N, E, self._restore_point)
+
+    def _latent_losses(self, cal_src, cal_tgt, aln_tgt, cal_actions, cal_nonterms, aln_actions, aln_nonterms):
+        """dyn_coef dyn_loss + calib_coef calib_loss of the "pair" step from the (L, B, E) embeddings, actions (L, B, A)
+        and nonterms (L, B): the two scans, both losses through the frozen inverse-dynamics model, and the way back to
+        the embeddings.  -> dyn_sums, cal_sums (each [NLL sum over the selected rows, selected rows]), d_cal_tgt (L, B, E)
+        with frame 0 zero, d_aln_tgt (T, B, E) for frames 1..L-1.  cal_src has no gradient path: its scan is never
+        reversed."""
+        c, dev, tm, inv = self.c, self.device, self.transition_model, self.inv_dynamics
+        L, B, E = cal_src.shape
+        T, D, S = L - 1, c.belief_size, c.state_size
+        F_, Nr = D + S, (T - 1) * B
+        # -- the scans (repo_adapt.py:271-294), one after the other on this stream: the column-split engine's exchange
+        # buffer and the status word are shared
+        pr, _ = self._pg(tm)
+        eps_p, eps_q = self._noise("cal_prior", (T, 3 * B, S)), self._noise("cal_post", (T, 3 * B, S))
+        cut = lambda e, lo, hi: None if e is None else e[:, lo:hi].contiguous()   # noqa: E731
+        draw = (lambda n: self._draw(n)) if eps_p is None else (lambda n: (0, 0))
+        emb = lambda e: e[1:]   # noqa: E731
+        b0, s0 = self._zero_state(B)
+        sv_s = ops.rssm_observe_fwd(pr, b0, s0, cal_actions[:-1], cal_nonterms[:-1], emb(cal_src), cut(eps_p, 0, B),
+                                    cut(eps_q, 0, B), tm.min_std_dev, noise=draw(2 * T * B * S), act=tm.act)
+        b0, s0 = self._zero_state(2 * B)
+        sv_t = ops.rssm_observe_fwd(pr, b0, s0, torch.cat((cal_actions[:-1], aln_actions[:-1]), 1),
+                                    torch.cat((cal_nonterms[:-1], aln_nonterms[:-1]), 1),
+                                    torch.cat((emb(cal_tgt), emb(aln_tgt)), 1), cut(eps_p, B, 3 * B), cut(eps_q, B, 3 * B),
+                                    tm.min_std_dev, noise=draw(2 * T * 2 * B * S), act=tm.act)
+        lat_s, lat_ct, lat_at = sv_s.featx[1:], sv_t.featx[1:, :B], sv_t.featx[1:, B:]
+        # -- both losses through the frozen inverse-dynamics model in one chain: rows [dyn | calib]
+        x = torch.empty(2 * Nr, F_ + D, device=dev)
+        ops.inv_dyn_pack_pair(lat_at, lat_at, D, out=x[:Nr])     # [aln belief_t | aln post_t | aln belief_t+1]
+        ops.inv_dyn_pack_pair(lat_s, lat_ct, D, out=x[Nr:])      # [src belief_t | src post_t | tgt belief_t+1]
+        pi, _ = self._pg(inv)
+        raw, hid = ops.mlp_fwd(pi, x, act=inv.act)
+        draw_ = torch.empty_like(raw)
+        A = aln_actions.shape[2]
+        dyn_sums, _ = ops.normal_nll_rows(raw[:Nr], aln_actions[1:-1].reshape(Nr, A), aln_nonterms[1:-1].reshape(Nr),
+                                          inv.min_std_dev, draw=draw_[:Nr])
+        cal_sums, _ = ops.normal_nll_rows(raw[Nr:], cal_actions[1:-1].reshape(Nr, A), cal_nonterms[1:-1].reshape(Nr),
+                                          inv.min_std_dev, draw=draw_[Nr:])
+        dx = torch.empty_like(x)
+        ops.mlp_bwd(pi, x, hid, draw_, dparams=None, dx=dx, act=inv.act)
+        # -- the coefficients enter where the rows' gradients go back to the latents; then the frozen reverse scan
+        dfeat = torch.empty(T, 2 * B, F_, device=dev)
+        ops.inv_dyn_unpack_pair(None, dx[Nr:], D, dfeat[:, :B], 0.0, c.calib_coef)
+        ops.inv_dyn_unpack_pair(dx[:Nr], dx[:Nr], D, dfeat[:, B:], c.dyn_coef, c.dyn_coef)
+        dembeds = torch.empty(T, 2 * B, E, device=dev)
+        ops.rssm_observe_bwd(pr, sv_t, None, dfeat=dfeat, dembeds=dembeds, min_std=tm.min_std_dev)
+        d_ct = torch.empty(L, B, E, device=dev)
+        d_ct[0].zero_()   # frame 0 never enters the scan
+        d_ct[1:] = dembeds[:, :B]
+        return dict(dyn_sums=dyn_sums, cal_sums=cal_sums, d_cal_tgt=d_ct, d_aln_tgt=dembeds[:, B:])
 
     def _flush_cal_log(self):
         if self._cal_log is None:
             return
-        ev, scales, N, E, support = self._cal_log
+        ev, scales, N, E, support, pair, n = self._cal_log
         self._cal_log = None
         ev.synchronize()
         h = self._cal_host.tolist()
         c = self.c
         f = {k: v * s for k, v, s in zip(("real", "fake", "kl", "gp", "beta"), h[:5], scales)}
-        aln, calib = h[5] / N, h[6] / (N * E) + 0.5 * LOG_2PI
-        out = {"train/f_loss_src": f["real"], "train/f_loss_tgt": f["fake"], "train/f_kl": f["kl"], "train/aln_loss": aln,
-               "train/calib_loss": calib, "train/encoder_loss": c.aln_coef * aln + c.calib_coef * calib}
-        self.last_grad_norms = {"encoder": max(h[7], 0.0) ** 0.5, "disc": max(h[8], 0.0) ** 0.5}
+        aln = h[5] / N
+        out = {"train/f_loss_src": f["real"], "train/f_loss_tgt": f["fake"], "train/f_kl": f["kl"], "train/aln_loss": aln}
+        if pair is None:
+            calib = h[6] / (N * E) + 0.5 * LOG_2PI
+            out.update({"train/calib_loss": calib, "train/encoder_loss": c.aln_coef * aln + c.calib_coef * calib})
+            h = h[7:]
+        else:
+            try:
+                self._raise_update_fault(int(self._cal_host[n - 1 : n].view(torch.int32).item()), pair)
+            except Exception as fault:  # noqa: BLE001  (RepoHipError)
+                raise type(fault)(f"{fault} -- of this calibration step the discriminator's own step (its Adam step and "
+                                  "beta) stands: it is not among the agent's optimisers") from None
+            # no selected row: the gradient was exact zeros and the log says nan, as the reference's mean over no rows
+            dyn, calib = (h[i] / h[i + 1] if h[i + 1] > 0 else float("nan") for i in (6, 8))
+            out.update({"train/dyn_loss": dyn, "train/calib_loss": calib,
+                        "train/encoder_loss": c.aln_coef * aln + c.dyn_coef * dyn + c.calib_coef * calib})
+            h = h[10:]
+        self.last_grad_norms = {"encoder": max(h[0], 0.0) ** 0.5, "disc": max(h[1], 0.0) ** 0.5}
         self.last_disc_scalars = {"gp": f["gp"], "beta": f["beta"]}
         if support:
-            tau_d, tau_m1, u_old, u_new, tsq = h[9:14]
+            tau_d, tau_m1, u_old, u_new, tsq = h[2:7]
             out["train/tau_loss"] = tau_d / N + u_old * tau_m1 / N
             out["train/tau_mean"] = 1.0 + tau_m1 / N
             out["train/u_value"] = u_new
@@ -351,13 +503,11 @@ class CalibratedRePo(RePo):
     def train_agent(self):
         """repo_adapt.py:484-491."""
         mode = self.c.calibration_mode
-        if mode == "pair":
-            raise NotImplementedError('calibration_mode="pair" (the frozen 3 B-row scan with the inverse-dynamics loss) is '
-                                      'not built; "simple_pair" is')
-        if mode != "simple_pair":
+        if mode not in ("pair", "simple_pair"):
             raise ValueError("Unsupported calibration mode")
+        step = self.pair_calibration if mode == "pair" else self.simple_pair_calibration
         for _ in range(self.c.train_steps):
-            self.simple_pair_calibration()
+            step()
         self._flush_cal_log()
 
     def train(self):

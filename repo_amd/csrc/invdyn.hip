@@ -1,5 +1,6 @@
 // The inverse-dynamics auxiliary (config.inv_dynamics; reference dreamer.py:220-239, models/utils.py:84-109): the two
-// passes around its dense chain.  repo_inv_dyn_pack forms the model's input rows from the observe scan's output, and
+// passes around its dense chain.  repo_inv_dyn_pack forms the model's input rows from the observe scan's output
+// (repo_inv_dyn_pack_pair from two column blocks of it, repo_inv_dyn_unpack_pair is that pack's adjoint), and
 // repo_normal_nll_rows is the masked Normal NLL of the action head with its gradient and the data-dependent row count.
 // Both are HBM-bound streaming kernels; the reduction follows loss.hip (wave64 shuffles, one partial per workgroup,
 // the launch's last block sums them in a fixed order: common.h, last_block_finishes -- no float atomics).
@@ -29,6 +30,50 @@ __global__ __launch_bounds__(256) void inv_dyn_pack_kernel(long total, int wv, i
     const int c = (int)(i - r * wv) * V;
     const float* src = c < F ? feat + r * ldfeat + c : feat + (r + B) * ldfeat + (c - F);
     *reinterpret_cast<T*>(x + r * ldx + c) = *reinterpret_cast<const T*>(src);
+  }
+}
+
+// The same rows from TWO column blocks of a wider scan output (CalibratedRePo's "pair" step):
+// x[t * B + b] = [cur[t][b][0:F] | next[t + 1][b][0:D]], each block with its own row pitch (ld) and time pitch (td).
+template <int V>
+__global__ __launch_bounds__(256) void inv_dyn_pack_pair_kernel(long total, int wv, int F, int B,
+                                                                const float* __restrict__ cur, long ldc, long tdc,
+                                                                const float* __restrict__ next, long ldn, long tdn,
+                                                                float* __restrict__ x, long ldx) {
+  using T = typename PackVec<V>::type;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long r = i / wv;
+    const int c = (int)(i - r * wv) * V;
+    const long t = r / B, b = r - t * B;
+    const float* src = c < F ? cur + t * tdc + b * ldc + c : next + (t + 1) * tdn + b * ldn + (c - F);
+    *reinterpret_cast<T*>(x + r * ldx + c) = *reinterpret_cast<const T*>(src);
+  }
+}
+
+// The adjoint of the pack in gather form: one thread per element (t, b, c) of the (T, B, F) block dfeat, no atomics.
+//   c < F, t <= T-2 (and dx_cur given):  scale_cur  * dx_cur[(t, b)][c]          the row's own [belief_t | state_t]
+//   c < D, t >= 1:                       scale_next * dx_next[(t-1, b)][F + c]   belief_t as the row before's "next"
+// Each term is one rounded multiply and their sum one rounded add (no contraction into an fma); an element neither term
+// reaches gets an exact zero, written.
+__global__ __launch_bounds__(256) void inv_dyn_unpack_pair_kernel(long total, int T, int B, int D, int F,
+                                                                  const float* __restrict__ dx_cur, long ldxc,
+                                                                  const float* __restrict__ dx_next, long ldxn,
+                                                                  float scale_cur, float scale_next,
+                                                                  float* __restrict__ dfeat, long ldf, long tdf,
+                                                                  int accumulate) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long tb = i / F;
+    const int c = (int)(i - tb * F);
+    const long t = tb / B, b = tb - t * B;
+    const bool has_cur = dx_cur && t <= T - 2, has_next = c < D && t >= 1;
+    float v = 0.f;
+    if (has_cur) v = __fmul_rn(scale_cur, dx_cur[(t * B + b) * ldxc + c]);
+    if (has_next) {
+      const float nx = __fmul_rn(scale_next, dx_next[((t - 1) * B + b) * ldxn + F + c]);
+      v = has_cur ? __fadd_rn(v, nx) : nx;
+    }
+    float* dst = dfeat + t * tdf + b * ldf + c;
+    *dst = accumulate ? __fadd_rn(*dst, v) : v;
   }
 }
 
@@ -125,6 +170,59 @@ extern "C" int repo_inv_dyn_pack(int64_t T, int64_t B, int64_t D, int64_t S, con
   else
     hipLaunchKernelGGL(inv_dyn_pack_kernel<1>, dim3(blocks), dim3(256), 0, stream, total, wv, (int)F, (int)B, featx,
                        (long)ldfeat, x, (long)ldx);
+  REPO_CHECK_LAUNCH();
+  return REPO_OK;
+}
+
+extern "C" int repo_inv_dyn_pack_pair(int64_t T, int64_t B, int64_t D, int64_t S, const float* cur, int64_t ldcur,
+                                      int64_t tdcur, const float* next, int64_t ldnext, int64_t tdnext, float* x,
+                                      int64_t ldx, hipStream_t stream) {
+  REPO_ARCH_GUARD();
+  const int64_t F = D + S, W = F + D, N = (T - 1) * B;
+  REPO_REQUIRE(T >= 2 && B > 0 && D > 0 && S > 0 && ldcur >= F && ldnext >= F && tdcur >= B * ldcur &&
+                   tdnext >= B * ldnext && ldx >= W,
+               REPO_E_SHAPE);
+  REPO_REQUIRE(T * tdcur < kMaxIdx && T * tdnext < kMaxIdx && N * ldx < kMaxIdx, REPO_E_SHAPE);
+  REPO_REQUIRE(cur && next && x, REPO_E_BADARG);
+  // the rule of repo_inv_dyn_pack with the column offsets (in the bases) and the time pitches included
+  int V = 1;
+  for (int v = 4; v > 1 && V == 1; v >>= 1)
+    if (F % v == 0 && D % v == 0 && ldcur % v == 0 && tdcur % v == 0 && ldnext % v == 0 && tdnext % v == 0 &&
+        ldx % v == 0 && aligned_to(cur, 4 * v) && aligned_to(next, 4 * v) && aligned_to(x, 4 * v))
+      V = v;
+  const int wv = (int)(W / V);
+  const long total = (long)N * wv;
+  const int blocks = (int)(cdiv(total, 256) > 4096 ? 4096 : cdiv(total, 256));
+  auto go = [&](auto k) {
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, stream, total, wv, (int)F, (int)B, cur, (long)ldcur, (long)tdcur,
+                       next, (long)ldnext, (long)tdnext, x, (long)ldx);
+  };
+  if (V == 4)
+    go(inv_dyn_pack_pair_kernel<4>);
+  else if (V == 2)
+    go(inv_dyn_pack_pair_kernel<2>);
+  else
+    go(inv_dyn_pack_pair_kernel<1>);
+  REPO_CHECK_LAUNCH();
+  return REPO_OK;
+}
+
+extern "C" int repo_inv_dyn_unpack_pair(int64_t T, int64_t B, int64_t D, int64_t S, const float* dx_cur, int64_t lddx_cur,
+                                        const float* dx_next, int64_t lddx_next, float scale_cur, float scale_next,
+                                        float* dfeat, int64_t lddfeat, int64_t tddfeat, int accumulate,
+                                        hipStream_t stream) {
+  REPO_ARCH_GUARD();
+  const int64_t F = D + S, W = F + D, N = (T - 1) * B;
+  REPO_REQUIRE(T >= 2 && B > 0 && D > 0 && S > 0 && lddfeat >= F && tddfeat >= B * lddfeat && lddx_next >= W &&
+                   (!dx_cur || lddx_cur >= W),
+               REPO_E_SHAPE);
+  REPO_REQUIRE(T * tddfeat < kMaxIdx && N * lddx_next < kMaxIdx && (!dx_cur || N * lddx_cur < kMaxIdx), REPO_E_SHAPE);
+  REPO_REQUIRE(dx_next && dfeat, REPO_E_BADARG);
+  const long total = (long)(T * B * F);
+  const int blocks = (int)(cdiv(total, 256) > 4096 ? 4096 : cdiv(total, 256));
+  hipLaunchKernelGGL(inv_dyn_unpack_pair_kernel, dim3(blocks), dim3(256), 0, stream, total, (int)T, (int)B, (int)D, (int)F,
+                     dx_cur, (long)lddx_cur, dx_next, (long)lddx_next, scale_cur, scale_next, dfeat, (long)lddfeat,
+                     (long)tddfeat, accumulate != 0);
   REPO_CHECK_LAUNCH();
   return REPO_OK;
 }

@@ -352,18 +352,22 @@ __global__ void prior_delta_kernel(int n, int S, const float* __restrict__ dstat
   }
 }
 
-extern "C" size_t repo_rssm_observe_bwd_workspace_bytes(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd,
-                                                        int64_t S, int64_t E) {
+// want_wgrad = false (repo_rssm_observe_bwd_frozen): the deltas, and a slab that holds the scan's own packs only
+static size_t obs_bwd_ws_bytes(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t E,
+                               bool want_wgrad) {
   // deltas + the largest wgrad slab
   const size_t rows = (size_t)T * B;
   size_t deltas = rows * (size_t)(4 * S + 2 * Hd + 6 * D + D);
-  // the seven recurrent-path weight gradients share one launch pair (one slab each); the (Hd x E) one runs alone
-  WgradDesc jobs[7];
-  obs_wgrad_jobs(jobs, T * B, B, A, D, Hd, S, E, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, nullptr, nullptr, nullptr);
-  size_t slab = gemm_wgrad_group_ws_bytes(jobs, 7);
-  const size_t big = repo_gemm_wgrad_workspace_bytes(T * B, Hd, E);
-  if (big > slab) slab = big;
+  size_t slab = 0;
+  if (want_wgrad) {
+    // the seven recurrent-path weight gradients share one launch pair (one slab each); the (Hd x E) one runs alone
+    WgradDesc jobs[7];
+    obs_wgrad_jobs(jobs, T * B, B, A, D, Hd, S, E, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, nullptr);
+    slab = gemm_wgrad_group_ws_bytes(jobs, 7);
+    const size_t big = repo_gemm_wgrad_workspace_bytes(T * B, Hd, E);
+    if (big > slab) slab = big;
+  }
   const size_t packs = bwd_pack_floats(A, D, Hd, S) * sizeof(float);  // live only during the scan kernel
   if (packs > slab) slab = packs;
   if (scan_cs_ok(T, B, A, D, Hd, S)) {  // column-split engine: its packs and exchange buffers + the prior head's d belief
@@ -373,23 +377,35 @@ extern "C" size_t repo_rssm_observe_bwd_workspace_bytes(int64_t T, int64_t B, in
   return deltas * sizeof(float) + slab + 256;
 }
 
-extern "C" int repo_rssm_observe_bwd_act(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t E,
-                                     const float* const* params, const float* nonterms, const float* embeds,
-                                     const float* eps_prior, const float* eps_post, uint64_t noise_seed,
-                                     uint64_t noise_offset, float min_std, const float* featx,
-                                     const float* prior_std, const float* post_std, const float* xsa, const float* e,
-                                     const float* gates, const float* hp, const float* hq, const float* dfeat,
-                                     const float* dprior_state, const float* dpm, const float* dps, const float* dqm,
-                                     const float* dqs, float* const* dparams, float* dembeds, float* dprev_belief,
-                                     float* dprev_state, int accumulate, unsigned* status, void* ws,
-                                     size_t ws_bytes, hipStream_t stream, int act) {
+extern "C" size_t repo_rssm_observe_bwd_workspace_bytes(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd,
+                                                        int64_t S, int64_t E) {
+  return obs_bwd_ws_bytes(T, B, A, D, Hd, S, E, true);
+}
+
+extern "C" size_t repo_rssm_observe_bwd_frozen_workspace_bytes(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd,
+                                                               int64_t S, int64_t E) {
+  return obs_bwd_ws_bytes(T, B, A, D, Hd, S, E, false);
+}
+
+// The reverse scan behind repo_rssm_observe_bwd_act (want_wgrad: the eight deferred weight-gradient products follow the
+// scan, dparams required) and repo_rssm_observe_bwd_frozen (the scan and d embeds only: dparams is not read).
+static int obs_bwd_run(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t E,
+                       const float* const* params, const float* nonterms, const float* embeds,
+                       const float* eps_prior, const float* eps_post, uint64_t noise_seed,
+                       uint64_t noise_offset, float min_std, const float* featx,
+                       const float* prior_std, const float* post_std, const float* xsa, const float* e,
+                       const float* gates, const float* hp, const float* hq, const float* dfeat,
+                       const float* dprior_state, const float* dpm, const float* dps, const float* dqm,
+                       const float* dqs, float* const* dparams, float* dembeds, float* dprev_belief,
+                       float* dprev_state, int accumulate, unsigned* status, void* ws,
+                       size_t ws_bytes, hipStream_t stream, int act, bool want_wgrad) {
   REPO_ARCH_GUARD();
   REPO_REQUIRE(act_ok(act), REPO_E_BADARG);
   REPO_REQUIRE(dims_ok(T, B, A, D, Hd, S) && E > 0 && T > 0, REPO_E_SHAPE);
   REPO_REQUIRE(params && nonterms && embeds && !eps_prior == !eps_post && featx && prior_std && post_std && xsa && e &&
-                   gates && hp && hq && dparams,
+                   gates && hp && hq && (dparams || !want_wgrad),
                REPO_E_BADARG);
-  REPO_REQUIRE(ws && ws_bytes >= repo_rssm_observe_bwd_workspace_bytes(T, B, A, D, Hd, S, E), REPO_E_WS_TOO_SMALL);
+  REPO_REQUIRE(ws && ws_bytes >= obs_bwd_ws_bytes(T, B, A, D, Hd, S, E, want_wgrad), REPO_E_WS_TOO_SMALL);
   const size_t rows = (size_t)T * B;
   float* w = (float*)ws;
   float* doutp = w;  w += rows * 2 * S;
@@ -411,18 +427,25 @@ extern "C" int repo_rssm_observe_bwd_act(int64_t T, int64_t B, int64_t A, int64_
     // column-split, weight-stationary reverse scan (scan_cs.hip).  The prior head is off the recurrence: its output
     // deltas, its hidden delta and its share of d belief_t are three launches over all T*B rows, in front of the scan
     REPO_REQUIRE(scan_cs_ok(T, B, A, D, Hd, S), REPO_E_SHAPE);
-    const int n = (int)(rows * S);
-    hipLaunchKernelGGL(prior_delta_kernel, dim3(cdiv(n, 256) > 1024 ? 1024 : cdiv(n, 256)), dim3(256), 0, stream, n, (int)S,
-                       dprior_state, dpm, dps, prior_std, NoiseSrc{eps_prior, noise_seed, noise_offset}, min_std, doutp);
-    REPO_CHECK_LAUNCH();
-    int rc1 = repo_gemm(0, 0, (int64_t)rows, Hd, 2 * S, doutp, 2 * S, P[8], Hd, nullptr, 1, dhp, Hd, act_epi_mul_d(act), hp,
-                        Hd, 0, stream);
-    if (rc1) return rc1;
-    float* dbx = (float*)slab;
-    if ((rc1 = repo_gemm(0, 0, (int64_t)rows, D, Hd, dhp, Hd, P[6], D, nullptr, 1, dbx, D, REPO_EPI_NONE, nullptr, 0, 0,
-                         stream)))
-      return rc1;
-    void* cws = (void*)(((uintptr_t)(dbx + rows * D) + 255) & ~(uintptr_t)255);
+    // no upstream on the prior head and nobody to read its deltas: the three launches would hand the scan zeros
+    const bool prior_dead = !want_wgrad && !dprior_state && !dpm && !dps;
+    int rc1 = REPO_OK;
+    float* dbx = nullptr;
+    void* cws = slab;
+    if (!prior_dead) {
+      const int n = (int)(rows * S);
+      hipLaunchKernelGGL(prior_delta_kernel, dim3(cdiv(n, 256) > 1024 ? 1024 : cdiv(n, 256)), dim3(256), 0, stream, n, (int)S,
+                         dprior_state, dpm, dps, prior_std, NoiseSrc{eps_prior, noise_seed, noise_offset}, min_std, doutp);
+      REPO_CHECK_LAUNCH();
+      rc1 = repo_gemm(0, 0, (int64_t)rows, Hd, 2 * S, doutp, 2 * S, P[8], Hd, nullptr, 1, dhp, Hd, act_epi_mul_d(act), hp,
+                      Hd, 0, stream);
+      if (rc1) return rc1;
+      dbx = (float*)slab;
+      if ((rc1 = repo_gemm(0, 0, (int64_t)rows, D, Hd, dhp, Hd, P[6], D, nullptr, 1, dbx, D, REPO_EPI_NONE, nullptr, 0, 0,
+                           stream)))
+        return rc1;
+      cws = (void*)(((uintptr_t)(dbx + rows * D) + 255) & ~(uintptr_t)255);
+    }
     ScanCsBwd q{T, B, A, D, Hd, S, E, params, nonterms,
                 NoiseSrc{eps_post, noise_seed, noise_offset + (uint64_t)(T * B * S)}, min_std,
                 featx, post_std, e, gates, hq, dfeat, dqm, dqs, dbx, doutq, dhq, dgi, dgh, de, dprev_belief, dprev_state, status, act};
@@ -473,19 +496,53 @@ extern "C" int repo_rssm_observe_bwd_act(int64_t T, int64_t B, int64_t A, int64_
   REPO_CHECK_LAUNCH();
 
   }
-  // deferred weight/bias gradients: (T*B)-row MFMA GEMMs
-  float* const* G = dparams;
   const int64_t R_ = (int64_t)rows;
   int rc;
-  WgradDesc jobs[7];
-  obs_wgrad_jobs(jobs, R_, B, A, D, Hd, S, E, featx, xsa, e, hp, hq, doutp, doutq, dhp, dhq, dgi, dgh, de, G);
-  if ((rc = gemm_wgrad_group(jobs, 7, accumulate, slab, slab_bytes, stream))) return rc;
-  // fc_embed_belief_posterior, columns [D, D+E): the embedding's share
-  if ((rc = repo_gemm_wgrad(R_, Hd, E, dhq, Hd, embeds, E, G[10] + D, D + E, nullptr, accumulate, slab, slab_bytes, stream))) return rc;
+  if (want_wgrad) {
+    // deferred weight/bias gradients: (T*B)-row MFMA GEMMs
+    float* const* G = dparams;
+    WgradDesc jobs[7];
+    obs_wgrad_jobs(jobs, R_, B, A, D, Hd, S, E, featx, xsa, e, hp, hq, doutp, doutq, dhp, dhq, dgi, dgh, de, G);
+    if ((rc = gemm_wgrad_group(jobs, 7, accumulate, slab, slab_bytes, stream))) return rc;
+    // fc_embed_belief_posterior, columns [D, D+E): the embedding's share
+    if ((rc = repo_gemm_wgrad(R_, Hd, E, dhq, Hd, embeds, E, G[10] + D, D + E, nullptr, accumulate, slab, slab_bytes, stream))) return rc;
+  }
   // gradient into the encoder embedding: d embeds = dhq @ W_bq[:, D:]
   if (dembeds)
     if ((rc = repo_gemm(0, 0, R_, E, Hd, dhq, Hd, P[10] + D, D + E, nullptr, 1, dembeds, E, REPO_EPI_NONE, nullptr, 0, 0, stream))) return rc;
   return REPO_OK;
+}
+
+extern "C" int repo_rssm_observe_bwd_act(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t E,
+                                         const float* const* params, const float* nonterms, const float* embeds,
+                                         const float* eps_prior, const float* eps_post, uint64_t noise_seed,
+                                         uint64_t noise_offset, float min_std, const float* featx,
+                                         const float* prior_std, const float* post_std, const float* xsa, const float* e,
+                                         const float* gates, const float* hp, const float* hq, const float* dfeat,
+                                         const float* dprior_state, const float* dpm, const float* dps, const float* dqm,
+                                         const float* dqs, float* const* dparams, float* dembeds, float* dprev_belief,
+                                         float* dprev_state, int accumulate, unsigned* status, void* ws,
+                                         size_t ws_bytes, hipStream_t stream, int act) {
+  return obs_bwd_run(T, B, A, D, Hd, S, E, params, nonterms, embeds, eps_prior, eps_post, noise_seed, noise_offset,
+                     min_std, featx, prior_std, post_std, xsa, e, gates, hp, hq, dfeat, dprior_state, dpm, dps, dqm, dqs,
+                     dparams, dembeds, dprev_belief, dprev_state, accumulate, status, ws, ws_bytes, stream, act, true);
+}
+
+// ABI v13: the same reverse scan for FROZEN weights -- no weight-gradient product, no slab for one
+extern "C" int repo_rssm_observe_bwd_frozen(int64_t T, int64_t B, int64_t A, int64_t D, int64_t Hd, int64_t S, int64_t E,
+                                            const float* const* params, const float* nonterms, const float* embeds,
+                                            const float* eps_prior, const float* eps_post, uint64_t noise_seed,
+                                            uint64_t noise_offset, float min_std, const float* featx,
+                                            const float* prior_std, const float* post_std, const float* xsa, const float* e,
+                                            const float* gates, const float* hp, const float* hq, const float* dfeat,
+                                            const float* dprior_state, const float* dpm, const float* dps, const float* dqm,
+                                            const float* dqs, float* dembeds, float* dprev_belief, float* dprev_state,
+                                            int engine, unsigned* status, void* ws, size_t ws_bytes, hipStream_t stream,
+                                            int act) {
+  REPO_REQUIRE(engine == 0 || engine == 2, REPO_E_BADARG);
+  return obs_bwd_run(T, B, A, D, Hd, S, E, params, nonterms, embeds, eps_prior, eps_post, noise_seed, noise_offset,
+                     min_std, featx, prior_std, post_std, xsa, e, gates, hp, hq, dfeat, dprior_state, dpm, dps, dqm, dqs,
+                     nullptr, dembeds, dprev_belief, dprev_state, engine, status, ws, ws_bytes, stream, act, false);
 }
 
 // ---- the pre-v9 entry points: the ELU instantiations

@@ -586,23 +586,32 @@ def rssm_observe_fwd(params, prev_belief, prev_state, actions, nonterms, embeds,
 
 def rssm_observe_bwd(params, sv, dparams, dfeat=None, dprior_state=None, dpm=None, dps=None, dqm=None, dqs=None,
                      dembeds=None, dprev_belief=None, dprev_state=None, accumulate=False, min_std=0.1, act=None):
-    """act: None (the activation `sv` remembers from its forward) or that same value; another one raises."""
+    """act: None (the activation `sv` remembers from its forward) or that same value; another one raises.
+    dparams=None: the transition weights are FROZEN -- the same reverse scan without its eight weight-gradient products
+    (repo_rssm_observe_bwd_frozen): dembeds, dprev_belief and dprev_state come out as with gradients."""
     act = _saved_act(sv, act)
     dev = sv.featx.device
-    nb = lib().repo_rssm_observe_bwd_workspace_bytes(sv.T, sv.B, sv.A, sv.D, sv.Hd, sv.S, sv.E)
+    L = lib()
+    frozen = dparams is None
+    assert not (frozen and accumulate), "accumulate adds to dparams"
+    query = L.repo_rssm_observe_bwd_frozen_workspace_bytes if frozen else L.repo_rssm_observe_bwd_workspace_bytes
+    nb = query(sv.T, sv.B, sv.A, sv.D, sv.Hd, sv.S, sv.E)
     ws = workspace(nb, dev)
-    pa, ga = ptr_array(params), ptr_array(dparams)
-    check(
-        lib().repo_rssm_observe_bwd_act(
-            sv.T, sv.B, sv.A, sv.D, sv.Hd, sv.S, sv.E, pa, _ptr(sv.nonterms), _ptr(sv.embeds), _ptr(sv.eps_prior),
-            _ptr(sv.eps_post), sv.noise[0], sv.noise[1], float(min_std), _ptr(sv.featx), _ptr(sv.prior_std), _ptr(sv.post_std), _ptr(sv.xsa),
-            _ptr(sv.e), _ptr(sv.gates), _ptr(sv.hp), _ptr(sv.hq), _ptr(dfeat), _ptr(dprior_state), _ptr(dpm),
-            _ptr(dps), _ptr(dqm), _ptr(dqs), ga, _ptr(dembeds), _ptr(dprev_belief), _ptr(dprev_state),
-            int(bool(accumulate)) | (2 if getattr(sv, "cs", False) else 0), _ptr(scan_status(dev)), _ptr(ws), ws.numel(),
-            _stream(), act,
-        ),
-        "repo_rssm_observe_bwd_act",
-    )
+    pa = ptr_array(params)
+    head = (sv.T, sv.B, sv.A, sv.D, sv.Hd, sv.S, sv.E, pa, _ptr(sv.nonterms), _ptr(sv.embeds), _ptr(sv.eps_prior),
+            _ptr(sv.eps_post), sv.noise[0], sv.noise[1], float(min_std), _ptr(sv.featx), _ptr(sv.prior_std), _ptr(sv.post_std),
+            _ptr(sv.xsa), _ptr(sv.e), _ptr(sv.gates), _ptr(sv.hp), _ptr(sv.hq), _ptr(dfeat), _ptr(dprior_state), _ptr(dpm),
+            _ptr(dps), _ptr(dqm), _ptr(dqs))
+    engine = 2 if getattr(sv, "cs", False) else 0
+    tail = (_ptr(scan_status(dev)), _ptr(ws), ws.numel(), _stream(), act)
+    if frozen:
+        check(L.repo_rssm_observe_bwd_frozen(*head, _ptr(dembeds), _ptr(dprev_belief), _ptr(dprev_state), engine, *tail),
+              "repo_rssm_observe_bwd_frozen")
+        return
+    ga = ptr_array(dparams)
+    check(L.repo_rssm_observe_bwd_act(*head, ga, _ptr(dembeds), _ptr(dprev_belief), _ptr(dprev_state),
+                                      int(bool(accumulate)) | engine, *tail),
+          "repo_rssm_observe_bwd_act")
 
 
 # ----------------------------------------------------------------------------- MLP heads
@@ -827,22 +836,68 @@ def inv_dyn_pack(featx, D, out=None):
     return out
 
 
-def normal_nll_rows(raw, target, mask, min_std=0.1, count_in=None, want_grad=True, out=None):
+def _block_pitches(t, what):
+    """(row pitch, time pitch) of a (T, B, F) float32 view with contiguous rows -- e.g. a column block of a wider scan
+    output."""
+    T, B, F = t.shape
+    assert t.dtype == torch.float32 and t.is_cuda and t.stride(2) == 1 and t.stride(1) >= F and \
+        t.stride(0) >= B * t.stride(1), (what, t.shape, t.stride())
+    return t.stride(1), t.stride(0)
+
+
+def inv_dyn_pack_pair(cur, nxt, D, out=None):
+    """The inverse-dynamics rows across TWO blocks (include/repo_hip.h, repo_inv_dyn_pack_pair): cur, nxt (T, B, D+S)
+    views with contiguous rows, each with its own pitches (column blocks sv.featx[1:, c0:c0+B] of a wider scan) ->
+    x ((T-1)*B, 2D+S), x[t*B+b] = [cur[t, b] | nxt[t+1, b, :D]].  `out`: rows of a larger buffer."""
+    T, B, F = cur.shape
+    assert tuple(nxt.shape) == (T, B, F), (cur.shape, nxt.shape)
+    D = int(D)
+    (ldc, tdc), (ldn, tdn) = _block_pitches(cur, "cur"), _block_pitches(nxt, "nxt")
+    if out is None:
+        out = torch.empty((T - 1) * B, F + D, dtype=torch.float32, device=cur.device)
+    assert tuple(out.shape) == ((T - 1) * B, F + D) and out.dtype == torch.float32 and out.stride(1) == 1, out.shape
+    check(lib().repo_inv_dyn_pack_pair(T, B, D, F - D, _ptr(cur), ldc, tdc, _ptr(nxt), ldn, tdn, _ptr(out), _ld(out),
+                                       _stream()), "repo_inv_dyn_pack_pair")
+    return out
+
+
+def inv_dyn_unpack_pair(dx_cur, dx_next, D, dfeat, scale_cur=1.0, scale_next=1.0, accumulate=False):
+    """The adjoint of inv_dyn_pack_pair in gather form (repo_inv_dyn_unpack_pair): dfeat (T, B, D+S), a view with its own
+    pitches, gets scale_cur * dx_cur[(t, b), :D+S] (t <= T-2) + scale_next * dx_next[(t-1, b), D+S:] (t >= 1, the belief
+    columns) in EVERY element, zeros included; accumulate: added to it.  dx_cur=None: the block only served as `next`."""
+    T, B, F = dfeat.shape
+    D = int(D)
+    N, W = (T - 1) * B, F + D
+    ldf, tdf = _block_pitches(dfeat, "dfeat")
+    assert dx_next is not None, "dx_next is required (dx_cur may be None)"
+    for d in (dx_cur, dx_next):
+        assert d is None or (tuple(d.shape) == (N, W) and d.dtype == torch.float32 and d.stride(1) == 1), (d.shape, N, W)
+    check(lib().repo_inv_dyn_unpack_pair(T, B, D, F - D, _ptr(dx_cur), _ld(dx_cur) if dx_cur is not None else 0,
+                                         _ptr(dx_next), _ld(dx_next), float(scale_cur), float(scale_next), _ptr(dfeat),
+                                         ldf, tdf, int(bool(accumulate)), _stream()), "repo_inv_dyn_unpack_pair")
+    return dfeat
+
+
+def normal_nll_rows(raw, target, mask, min_std=0.1, count_in=None, want_grad=True, out=None, draw=None):
     """Masked Normal NLL of a [mean | pre-softplus std] head over the rows with mask == 1 (include/repo_hip.h,
     repo_normal_nll_rows): raw (N, 2A) and target (N, A) views with contiguous rows, mask (N,).  Returns (sums =
     [NLL sum over the selected rows, selected rows], draw = the gradient of the MEAN loss w.r.t. raw, or None);
-    count_in: a device float that replaces the kernel's own count as the gradient's divisor (data parallel)."""
+    count_in: a device float that replaces the kernel's own count as the gradient's divisor (data parallel).
+    draw: an optional (N, 2A) view with contiguous rows for the gradient (e.g. rows of a larger buffer)."""
     N, A2 = raw.shape
     A = A2 // 2
     dev = raw.device
     assert A2 == 2 * A and tuple(target.shape) == (N, A) and mask.numel() == N, (raw.shape, target.shape, mask.shape)
-    draw = torch.empty(N, A2, dtype=torch.float32, device=dev) if want_grad else None
+    if draw is None:
+        draw = torch.empty(N, A2, dtype=torch.float32, device=dev) if want_grad else None
+    assert draw is None or (want_grad and tuple(draw.shape) == (N, A2) and draw.dtype == torch.float32 and draw.is_cuda
+                            and draw.stride(1) == 1), (draw.shape, draw.dtype, draw.stride(), N, A2)
     if out is None:
         out = torch.empty(2, dtype=torch.float32, device=dev)
     ws = reduce_ws(dev, lib().repo_normal_nll_rows_workspace_bytes())
     check(
         lib().repo_normal_nll_rows(N, A, _ptr(raw), _ld(raw), _ptr(target), _ld(target), _ptr(_f32c(mask)),
-                                   _ptr(count_in), float(min_std), _ptr(out), _ptr(draw), 2 * A if want_grad else 0,
+                                   _ptr(count_in), float(min_std), _ptr(out), _ptr(draw), _ld(draw) if want_grad else 0,
                                    _ptr(ws), ws.numel(), _stream()),
         "repo_normal_nll_rows",
     )

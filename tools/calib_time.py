@@ -5,18 +5,21 @@ step remain; the alignment gradient is a constant tensor).  Three rings mirrored
 + 20 timed steps; each measurement runs in a fresh child process, alternating.
 usage: python tools/calib_time.py                      js, js-stub, support, support-stub, twice, then the discriminator's kernels
        python tools/calib_time.py MODE [stub]          one measurement in this process (MODE: js | support)
+       python tools/calib_time.py pair                 the calibration_mode="pair" step against the simple_pair step:
+                                                       js simple_pair, js pair, support simple_pair, support pair, three times
+       python tools/calib_time.py MODE pair            one measurement of the "pair" step in this process
        python tools/calib_time.py kernels MODE         device time of every kernel of one VDBDiscriminator.train call"""
 import os, subprocess, sys, time
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, HERE)
 
 
-def make_agent(mode):
+def make_agent(mode, calibration="simple_pair"):
     import numpy as np
     import bench
     from repo_amd.algorithms.repo import CalibratedRePo
     cfg = bench.config("repo")
-    for k, v in dict(inv_dynamics=True, inv_dynamics_lr=3e-4, inv_dynamics_hidden_size=512, calibration_mode="simple_pair",
+    for k, v in dict(inv_dynamics=True, inv_dynamics_lr=3e-4, inv_dynamics_hidden_size=512, calibration_mode=calibration,
                      alignment_mode=mode, calibration_buffer_size=5000, expert_calib_data=True, calib_time_limit=500,
                      aln_coef=1.0, dyn_coef=1.0, calib_coef=1.0, f_lr=3e-4, f_latent_size=64, f_target_kl=0.1,
                      f_hidden_size=256, tau_lr=5e-5, u_lr=5e-3, init_u=1e-4, source_dir="", offline_truncate_size=1000000,
@@ -57,9 +60,9 @@ def stub_discriminator(agent):
     agent.log_tau.bwd = lambda *a, **k: None
 
 
-def measure(mode, stub):
+def measure(mode, stub, calibration="simple_pair"):
     import torch
-    agent, cfg = make_agent(mode)
+    agent, cfg = make_agent(mode, calibration)
     if stub:
         stub_discriminator(agent)
     cfg.train_steps = 5
@@ -69,7 +72,7 @@ def measure(mode, stub):
     agent.train_agent(); torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     what = "discriminator stubbed out (encoder only)" if stub else "whole step"
-    print(f"alignment_mode={mode}, {what}: {dt/20*1e3:.3f} ms per simple_pair_calibration step incl. sampling"
+    print(f"alignment_mode={mode}, {what}: {dt/20*1e3:.3f} ms per {calibration}_calibration step incl. sampling"
           + ("" if stub else f"; encoder_loss {agent.last_scalars['train/encoder_loss']:.4f}"), flush=True)
 
 
@@ -108,8 +111,14 @@ if __name__ == "__main__":
     me = os.path.abspath(__file__)
     if len(sys.argv) > 2 and sys.argv[1] == "kernels":
         kernels(sys.argv[2])
+    elif len(sys.argv) > 2 and sys.argv[1] in ("js", "support") and sys.argv[2] == "pair":
+        measure(sys.argv[1], False, "pair")
     elif len(sys.argv) > 1 and sys.argv[1] in ("js", "support"):
         measure(sys.argv[1], len(sys.argv) > 2 and sys.argv[2] == "stub")
+    elif len(sys.argv) > 1 and sys.argv[1] == "pair":
+        for _ in range(3):
+            for args in (["js"], ["js", "pair"], ["support"], ["support", "pair"]):
+                subprocess.run([sys.executable, me, *args], cwd=HERE, check=True, timeout=240)
     else:
         for _ in range(2):
             for args in (["js"], ["js", "stub"], ["support"], ["support", "stub"]):
