@@ -139,7 +139,8 @@ int repo_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t offset, hi
  * F.linear in models/rssm.py:36-64, models/decoder.py:42,191-194,
  * models/actor_critic.py:21-25,77-82 (transa=0, transb=1), their input gradients
  * (transb=0), and the 1x1 -> 5x5 first transposed convolution of the decoder
- * (models/decoder.py:44), which is a plain GEMM against the (1024, 128*25) weight.
+ * (models/decoder.py:44), which is a plain GEMM against the (E, 128*25) weight, E = config.embedding_size
+ * (1024 by default; any width: the encoder's fc 1024 -> E and its gradients are products of this entry and repo_gemm_wgrad too).
  * bias may be NULL; aux (ld = ldaux) is read only by the MUL_* / FILM epilogues.
  * bias_div < 0 (ABI v8, REPO_EPI_FILM_RELU only): the bias is per output column (as bias_div = 1) while the FiLM table's
  * channel of column n is n / -bias_div -- the decoder's COMPOSED first layers (repo_amd/functional.py, dec_head_compose:
@@ -790,7 +791,7 @@ int repo_dual_step_tasks(int64_t C, float* log_beta, float* exp_avg, float* exp_
 
 /* dst[c * ldd + r] = src[r * lds + c] for r < rows, c < cols; columns [rows, ldd) of dst are written as zeros
  * (ldd - rows < 64; lds, ldd multiples of 4, 16-byte aligned pointers).  The host side uses it to hand the bf16x6 dense
- * engine (repo_gemm) k-contiguous operands for the decoder's 1024 -> 3200 layer: forward on W^T (the reference's
+ * engine (repo_gemm) k-contiguous operands for the decoder's E -> 3200 layer (E = config.embedding_size): forward on W^T (the reference's
  * ConvTranspose2d weight keeps its (in, out, kH, kW) layout: models/decoder.py:43), weight gradient on the transposed
  * activations -- torch's counterpart is the .t() view that at::mm resolves inside the BLAS call. */
 int repo_transpose(int64_t rows, int64_t cols, const float* src, int64_t lds, float* dst, int64_t ldd,

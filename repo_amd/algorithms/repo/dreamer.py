@@ -310,7 +310,7 @@ class Dreamer:
         pd, _ = self._pg(self.obs_model)
         # the decoder's composed first layers (functional.dec_head_compose) depend on the parameters only: made here, under
         # the latency-bound scan, off the decoder's chain
-        head = Fn.dec_head_compose(pd) if not self._symbolic and Fn._dec_compose(rows) else None
+        head = Fn.dec_head_compose(pd) if not self._symbolic and Fn._dec_compose(rows, pd) else None
         sv = ops.rssm_observe_fwd(
             pr, b0, s0, actions[:-1].contiguous(), nonterms[:-1].reshape(T, B).contiguous(), embeds.view(T, B, -1),
             self._noise("obs_prior", (T, B, S)), self._noise("obs_post", (T, B, S)), self.transition_model.min_std_dev,

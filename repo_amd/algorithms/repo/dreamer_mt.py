@@ -97,7 +97,7 @@ class MultitaskDreamer(Dreamer):
         pr, _ = self._pg(self.transition_model)
         pd, _ = self._pg(self.obs_model)
         # the decoder's composed first layers (functional.dec_head_compose): parameters only, made under the scan
-        head = Fm.dec_head_compose(pd) if (Fm._fused() and Fm._dec_compose(rows)) else None
+        head = Fm.dec_head_compose(pd) if (Fm._fused() and Fm._dec_compose(rows, pd)) else None
         pseudo = torch.cat((actions[:-1], tasks[:-1]), dim=2).contiguous()
         sv = ops.rssm_observe_fwd(
             pr, *self._zero_state(B), pseudo,

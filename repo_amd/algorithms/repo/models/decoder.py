@@ -2,10 +2,12 @@
 (reference: algorithms/repo/models/decoder.py:6-48,178-195)."""
 import torch.nn as nn
 
+from .encoder import check_embedding_size
+
 
 class VisualObservationModel(nn.Module):
-    """Linear(230->1024) -> convT 1024->128 (k5) -> 64 (k5) -> 32 (k6) -> 3 (k6), stride 2, ReLU
-    between.  Children hold parameters only; see repo_amd.functional.decoder_*."""
+    """Linear(230->E) -> convT E->128 (k5) -> 64 (k5) -> 32 (k6) -> 3 (k6), stride 2, ReLU
+    between; E = embedding_size (1024 by default).  Children hold parameters only; see repo_amd.functional.decoder_*."""
 
     def __init__(self, belief_size, state_size, embedding_size, activation_function="relu", image_size=64):
         """image_size=128 (build-defined, see VisualEncoder): conv4 becomes 32 -> 16 (k6, 30 -> 64, ReLU) and
@@ -13,8 +15,7 @@ class VisualObservationModel(nn.Module):
         super().__init__()
         if activation_function != "relu":
             raise NotImplementedError("HIP decoder kernels fuse ReLU (cnn_activation_function='relu')")
-        if embedding_size != 1024:
-            raise NotImplementedError("embedding_size != 1024 is not on the hot path")
+        embedding_size = check_embedding_size(embedding_size)
         if image_size not in (64, 128):
             raise NotImplementedError(f"{image_size} x {image_size} frames: only 64 (the reference) and 128 (build-defined) are built")
         self.embedding_size = embedding_size
@@ -47,8 +48,7 @@ class TIAObservationModel(nn.Module):
         super().__init__()
         if activation_function != "relu":
             raise NotImplementedError("HIP decoder kernels fuse ReLU (cnn_activation_function='relu')")
-        if embedding_size != 1024:
-            raise NotImplementedError("embedding_size != 1024 is not on the hot path")
+        embedding_size = check_embedding_size(embedding_size)
         self.embedding_size = embedding_size
         self.fc1 = nn.Linear(belief_size + state_size, embedding_size)
         self.conv1 = nn.ConvTranspose2d(embedding_size, 128, 5, stride=2)

@@ -5,9 +5,17 @@ import torch.nn as nn
 from .... import functional as Fn
 
 
+def check_embedding_size(embedding_size):
+    """config.embedding_size of the pixel stacks: any positive integer (1024: the encoder has no fc)."""
+    if isinstance(embedding_size, bool) or int(embedding_size) != embedding_size or embedding_size < 1:
+        raise ValueError(f"embedding_size must be a positive integer, not {embedding_size!r}")
+    return int(embedding_size)
+
+
 class VisualEncoder(nn.Module):
-    """3x64x64 -> 32x31x31 -> 64x14x14 -> 128x6x6 -> 256x2x2 (k4, s2, ReLU), flattened to 1024
-    (image_size=128: -> 256x6x6, then fc 9216 -> 1024).
+    """3x64x64 -> 32x31x31 -> 64x14x14 -> 128x6x6 -> 256x2x2 (k4, s2, ReLU), flattened to 1024, then
+    `fc` = Identity if embedding_size == 1024 else Linear(1024, embedding_size), without an activation
+    (reference models/encoder.py:30-32,40; image_size=128: -> 256x6x6, then fc 9216 -> embedding_size).
 
     The nn.Conv2d children are parameter containers only (same constructors, hence the same
     default initialisation and state_dict names as the reference); arithmetic runs in the HIP
@@ -20,8 +28,7 @@ class VisualEncoder(nn.Module):
         super().__init__()
         if activation_function != "relu":
             raise NotImplementedError("HIP encoder kernels fuse ReLU (cnn_activation_function='relu')")
-        if embedding_size != 1024:
-            raise NotImplementedError("embedding_size != 1024 (extra fc layer) is not on the hot path")
+        embedding_size = check_embedding_size(embedding_size)
         if image_size not in (64, 128):
             raise NotImplementedError(f"{image_size} x {image_size} frames: only 64 (the reference) and 128 (build-defined) are built")
         self.embedding_size = embedding_size
@@ -30,11 +37,14 @@ class VisualEncoder(nn.Module):
         self.conv2 = nn.Conv2d(32, 64, 4, stride=2)
         self.conv3 = nn.Conv2d(64, 128, 4, stride=2)
         self.conv4 = nn.Conv2d(128, 256, 4, stride=2)
-        self.fc = nn.Identity() if image_size == 64 else nn.Linear(256 * 6 * 6, embedding_size)
+        if image_size == 64:   # registered behind conv4 as in the reference: same default initialisation and state_dict order
+            self.fc = nn.Identity() if embedding_size == 1024 else nn.Linear(1024, embedding_size)
+        else:
+            self.fc = nn.Linear(256 * 6 * 6, embedding_size)
 
     def plist(self):
         ps = [t for c in (self.conv1, self.conv2, self.conv3, self.conv4) for t in (c.weight, c.bias)]
-        if self.image_size == 128:
+        if isinstance(self.fc, nn.Linear):
             ps += [self.fc.weight, self.fc.bias]
         return ps
 

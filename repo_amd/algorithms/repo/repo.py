@@ -72,7 +72,7 @@ class RePo(Dreamer):
         pr, gr = self._pg(self.transition_model)
         pd, gd = self._pg(self.obs_model)
         # the decoder's composed first layers depend on the parameters only: made here, under the latency-bound scan
-        head = Fn.dec_head_compose(pd) if Fn._dec_compose(rows) else None
+        head = Fn.dec_head_compose(pd) if Fn._dec_compose(rows, pd) else None
         sv = ops.rssm_observe_fwd(
             pr, *self._zero_state(B), actions[:-1].contiguous(),
             nonterms[:-1].reshape(T, B).contiguous(), embeds.view(T, B, -1), self._noise("obs_prior", (T, B, S)),

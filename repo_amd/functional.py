@@ -13,15 +13,16 @@ from . import ops
 
 # ----------------------------------------------------------------------------- encoder
 # layer ids per frame size: the reference's 64 x 64 stack, and the build-defined 128 x 128 one (BASELINE config 4's
-# size; same kernel sizes, 256x6x6 flatten + a linear `fc` 9216 -> 1024: p then has ten tensors)
+# size; same kernel sizes, 256x6x6 flatten + a linear `fc` 9216 -> E).  The stack is keyed on the frame size; at 64 x 64 p
+# has ten tensors too when embedding_size != 1024 (the reference's optional `fc` 1024 -> E behind conv4), eight otherwise
 _ENC = {64: (ops.ENC1, ops.ENC2, ops.ENC3, ops.ENC4), 128: (ops.X_ENC1, ops.X_ENC2, ops.X_ENC3, ops.X_ENC4)}
 
 
 def encoder_fwd(p, obs):
     """VisualEncoder.forward (models/encoder.py:34-41).  obs (n,3,64,64) [or (n,3,128,128)] uint8 or float32.
-    p = [conv1.w, conv1.b, ..., conv4.w, conv4.b (, fc.w, fc.b)].  Returns (embeds (n,1024), saved)."""
+    p = [conv1.w, conv1.b, ..., conv4.w, conv4.b (, fc.w, fc.b)].  Returns (embeds (n, E), saved); E = 1024 without fc."""
     L = _ENC[obs.shape[-1]]
-    if len(p) > 8:   # the 128 x 128 stack (its data gradients take other engines: no masks)
+    if obs.shape[-1] == 128:   # the 128 x 128 stack (its data gradients take other engines: no masks)
         h1 = ops.conv_down(L[0], obs, p[0], p[1], epi=ops.EPI_RELU)
         h2 = ops.conv_down(L[1], h1, p[2], p[3], epi=ops.EPI_RELU)
         h3 = ops.conv_down(L[2], h2, p[4], p[5], epi=ops.EPI_RELU)
@@ -37,7 +38,9 @@ def encoder_fwd(p, obs):
     h2, m2 = ops.conv_down(L[1], h1, p[2], p[3], epi=ops.EPI_RELU, want_cmask=True)
     h3, m3 = ops.conv_down(L[2], h2, p[4], p[5], epi=ops.EPI_RELU, want_cmask=True)
     h4 = ops.conv_down(L[3], h3, p[6], p[7], epi=ops.EPI_RELU)
-    return h4.view(h4.shape[0], -1), (h1, h2, h3, h4, m1, m2, m3)
+    flat = h4.view(h4.shape[0], -1)
+    embeds = ops.gemm(flat, p[8], transb=True, bias=p[9]) if len(p) > 8 else flat   # fc (embedding_size != 1024): no activation
+    return embeds, (h1, h2, h3, h4, m1, m2, m3)
 
 
 class _Fork:
@@ -69,17 +72,21 @@ class _Fork:
 
 
 def encoder_bwd(p, obs, saved, dembeds, g, accumulate=False, side=None):
-    """Gradients of all eight encoder tensors into g (same order as p)."""
+    """Gradients of all encoder tensors (eight, ten with an fc) into g (same order as p)."""
     h1, h2, h3, h4 = saved[:4]
     masks = saved[4:] if len(saved) > 4 else None
     n = h4.shape[0]
     L = _ENC[obs.shape[-1]]
     fk = _Fork(side)
-    if len(p) > 8:  # the 128 x 128 stack's fc: d flatten = d embeds @ W, dW = d embeds^T @ flatten
+    if obs.shape[-1] == 128:  # the 128 x 128 stack's fc: d flatten = d embeds @ W, dW = d embeds^T @ flatten
         flat = h4.view(n, -1)
         dflat = ops.gemm(dembeds, p[8])
         fk.run(lambda: ops.gemm_wgrad(dembeds, flat, dW=g[8], db=g[9], accumulate=accumulate))
         d4 = ops.relu_mask(dflat.view(h4.shape), h4)
+    elif len(p) > 8:          # the 64 x 64 stack's fc: d h4 = (d embeds @ W) * relu'(h4) in the product's epilogue
+        flat = h4.view(n, -1)
+        d4 = ops.gemm(dembeds, p[8], epi=ops.EPI_MUL_DRELU, aux=flat).view(h4.shape)
+        fk.run(lambda: ops.gemm_wgrad(dembeds, flat, dW=g[8], db=g[9], accumulate=accumulate))
     else:
         d4 = ops.relu_mask(dembeds.reshape(h4.shape).contiguous(), h4)
     fk.run(lambda: ops.conv_wgrad(L[3], d4, h3, dw=g[6], db=g[7], accumulate=accumulate))
@@ -102,29 +109,37 @@ def encoder_bwd(p, obs, saved, dembeds, g, accumulate=False, side=None):
 
 # ----------------------------------------------------------------------------- decoder
 # The decoder's first two layers are LINEAR in sequence: `hidden = self.fc1(cat)  # No nonlinearity here`, then
-# `act(conv1(hidden.view(-1, E, 1, 1)))` (models/decoder.py:41-44) -- a (230 -> 1024) Linear followed by a
-# (1024 -> 128 x 5 x 5) transposed conv on a 1 x 1 input, which is a (1024 -> 3200) Linear.  Their composition is one
-# (230 -> 3200) Linear, W01 = W1^T W0 (3200 x 230), b01 = W1^T b0 + b1: the 1024-wide hidden never has to exist, and
-# neither do the three largest GEMMs of the update (forward 2450 x 3200 x 1024, input gradient 2450 x 1024 x 3200, weight
-# gradient 1024 x 3200 over 2450 rows: 16 GFLOP each).  With G = d1^T feat (3200 x 230) and s = column sums of d1:
+# `act(conv1(hidden.view(-1, E, 1, 1)))` (models/decoder.py:41-44) -- a (230 -> E) Linear followed by an
+# (E -> 128 x 5 x 5) transposed conv on a 1 x 1 input, which is an (E -> 3200) Linear; E = embedding_size.  Their composition
+# is one (230 -> 3200) Linear, W01 = W1^T W0 (3200 x 230), b01 = W1^T b0 + b1: the E-wide hidden never has to exist, and
+# at E = 1024 neither do the three largest GEMMs of the update (forward 2450 x 3200 x 1024, input gradient 2450 x 1024 x
+# 3200, weight gradient 1024 x 3200 over 2450 rows: 16 GFLOP each).  With G = d1^T feat (3200 x 230) and s = column sums of d1:
 #     h1   = relu(feat W01^T + b01)
 #     d W1 = W0 G^T + b0 s^T,   d W0 = W1 G,   d b0 = W1 s,   d b1 = channel sums of d1,   d feat = d1 W01
-# -- 5 / 7-10 GFLOP forward / backward instead of 17 / 34, exact in real arithmetic (fp32 rounding differs at the 1e-6
+# -- at E = 1024 5 / 7-10 GFLOP forward / backward instead of 17 / 34, exact in real arithmetic (fp32 rounding differs at the 1e-6
 # level, as between any two summation orders).  The bias terms ride as a 231st column (W0 | b0), (G | s): the vector
 # products b0^T W1 and W1 s alone are one-row GEMMs that cost 90-155 us on the tile engines (measured:
 # tools/probe_py/dec_head_compose.py); W1 G is a reduction over 3200 "rows" of W1^T and goes to the row-split weight-gradient
-# engine.  From _DEC_COMPOSE_MIN_ROWS rows up (composing costs 1.5 GFLOP whatever the batch: the acting path's single row
-# keeps the two layers); REPO_DEC_COMPOSE=0 restores the two-layer form everywhere.
+# engine.  From _DEC_COMPOSE_MIN_ROWS rows up (composing costs 1.5 GFLOP at E = 1024 whatever the batch: the acting path's
+# single row keeps the two layers); REPO_DEC_COMPOSE=0 restores the two-layer form everywhere.
+# Whether composing pays also depends on E.  Per pass over `rows` the composed head multiplies rows x F x 3200, the two
+# layers rows x E x (F + 3200); composing itself adds 3200 x E x pad per parameter state, which the row threshold covers.
+# So: compose when E (F + 3200) > F 3200 -- at F = 230 from E = 215 up, and at E = 1024 for every F below 1506 (today's
+# answer at every row count).  This is a count of multiplications, NOT a measurement: no narrow width has been timed in either form.
 _DEC_COMPOSE_MIN_ROWS = 512
 
 
-def _dec_compose(rows):
-    return rows >= _DEC_COMPOSE_MIN_ROWS and os.environ.get("REPO_DEC_COMPOSE", "1") == "1"
+def _dec_compose(rows, p):
+    """p: the decoder's parameter list (fc1.weight (E, F) first)."""
+    if rows < _DEC_COMPOSE_MIN_ROWS or os.environ.get("REPO_DEC_COMPOSE", "1") != "1":
+        return False
+    E, F_ = p[0].shape
+    return E * (F_ + 3200) > F_ * 3200
 
 
 class DecHead:
     """The composed first two decoder layers of one parameter state, F = belief + state inputs (230 by default):
-    w0aug (1024, pad) = [W0 | b0 | 0], w1t (3200, 1024) = W1^T, w01aug (3200, pad) = W1^T w0aug = [W01 | W1^T b0 | 0],
+    w0aug (E, pad) = [W0 | b0 | 0], w1t (3200, E) = W1^T, w01aug (3200, pad) = W1^T w0aug = [W01 | W1^T b0 | 0],
     b01 (3200,); pad = F + 1 (the bias column) rounded up to a multiple of 4 (232 at F = 230)."""
     __slots__ = ("w0aug", "w1t", "w01aug", "b01", "pad")
 
@@ -132,14 +147,14 @@ class DecHead:
 def dec_head_compose(p):
     """Depends on the parameters only: the agents issue it ahead of the scan, off the decoder's chain."""
     w0, b0 = p[0], p[1]
-    w1 = p[2].view(p[2].shape[0], -1)                        # (1024, 3200)
+    w1 = p[2].view(p[2].shape[0], -1)                        # (E, 3200)
     F_ = w0.shape[1]
     dh = DecHead()
     dh.pad = (F_ + 1 + 3) // 4 * 4
     dh.w0aug = torch.zeros(w0.shape[0], dh.pad, dtype=torch.float32, device=w0.device)
     dh.w0aug[:, :F_].copy_(w0)
     dh.w0aug[:, F_].copy_(b0)
-    dh.w1t = ops.transpose(w1)                                # (3200, 1024)
+    dh.w1t = ops.transpose(w1)                                # (3200, E)
     dh.w01aug = ops.gemm(dh.w1t, dh.w0aug)                    # (3200, pad)
     dh.b01 = dh.w01aug[:, F_] + p[3].repeat_interleave(w1.shape[1] // p[3].shape[0])
     return dh
@@ -159,13 +174,13 @@ def decoder_trunk_fwd(p, feat, head=None):
     ahead of time by dec_head_compose)."""
     rows = feat.shape[0]
     pk2, pk3 = ops.conv_up_pack(ops.DEC2, p[4]), ops.conv_up_pack(ops.DEC3, p[6])
-    if _dec_compose(rows):
+    if _dec_compose(rows, p):
         h0 = head if head is not None else dec_head_compose(p)
         F_ = _head_input(h0, p, feat)
         h1 = ops.gemm(feat, h0.w01aug[:, :F_], transb=True, bias=h0.b01, epi=ops.EPI_RELU).view(rows, 128, 5, 5)
     else:
         h0 = ops.gemm(feat, p[0], transb=True, bias=p[1])
-        w1 = p[2].view(p[2].shape[0], -1)  # (1024, 128*25): 1x1 -> 5x5 transposed conv is a GEMM
+        w1 = p[2].view(p[2].shape[0], -1)  # (E, 128*25): 1x1 -> 5x5 transposed conv is a GEMM
         h1 = ops.gemm(h0, w1, bias=p[3], bias_div=25, epi=ops.EPI_RELU).view(rows, 128, 5, 5)
     h2 = ops.conv_up(ops.DEC2, h1, p[4], p[5], epi=ops.EPI_RELU, pack=pk2)
     h3 = ops.conv_up(ops.DEC3, h2, p[6], p[7], epi=ops.EPI_RELU, pack=pk3)
@@ -293,7 +308,7 @@ def _decoder_bwd_tail(p, feat, h0, h1, h2, d3, g, dfeat, accumulate_dfeat, accum
         def wpair():
             ops.gemm(h0.w0aug, gaug, transb=True, out=g[2].view(w1.shape), accumulate=accumulate)   # d W1 = W0 G^T + b0 s^T
             ops.channel_sum(d1.view(rows, 128, 25), out=g[3], accumulate=accumulate)
-            d0aug, _ = ops.gemm_wgrad(h0.w1t, gaug, want_bias=False)                                # (1024, pad) = [W1 G | W1 s | 0]
+            d0aug, _ = ops.gemm_wgrad(h0.w1t, gaug, want_bias=False)                                # (E, pad) = [W1 G | W1 s | 0]
             if accumulate:
                 g[0].add_(d0aug[:, :F_])
                 g[1].add_(d0aug[:, F_])

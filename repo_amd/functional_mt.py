@@ -41,33 +41,44 @@ def _fused():
     return os.environ.get("REPO_FILM_FUSED", "1") == "1"
 
 
+def _enc_fc(p, h4):
+    flat = h4.view(h4.shape[0], -1)
+    return ops.gemm(flat, p[8], transb=True, bias=p[9]) if len(p) > 10 else flat
+
+
 def cond_encoder_fwd(p, obs, cond):
-    """p = [conv1.w, conv1.b, ..., conv4.w, conv4.b, film.w, film.b]; obs (n,3,64,64) uint8 | float32 in [-1,1];
-    cond (n, C).  Returns (embeds (n, 1024), saved)."""
-    film = _film(p[8], p[9], cond)
+    """p = [conv1.w, conv1.b, ..., conv4.w, conv4.b (, fc.w, fc.b), film.w, film.b]; obs (n,3,64,64) uint8 | float32 in
+    [-1,1]; cond (n, C).  Returns (embeds (n, E), saved); the fc 1024 -> E is there when embedding_size != 1024, behind the
+    FiLM'd conv4 and without an activation (the FiLM tensors are addressed from the end of p)."""
+    film = _film(p[-2], p[-1], cond)
     if _fused():
         tabs = ops.film_tables(film, ENC_CHANNELS)
         x, hs = obs, []
         for l in range(4):
             x = ops.conv_down(_ENC_L[l], x, p[2 * l], p[2 * l + 1], epi=ops.EPI_FILM_RELU, aux=tabs[l])
             hs.append(x)
-        return x.view(x.shape[0], -1), (film, None, hs)
+        return _enc_fc(p, x), (film, None, hs)
     x, ys, hs = obs, [], []
     for l in range(4):
         y = ops.conv_down(_ENC_L[l], x, p[2 * l], p[2 * l + 1], epi=ops.EPI_NONE)
         x = ops.film_fwd(y, film, *_ENC_OFF[l])
         ys.append(y)
         hs.append(x)
-    return x.view(x.shape[0], -1), (film, ys, hs)
+    return _enc_fc(p, x), (film, ys, hs)
 
 
 def cond_encoder_bwd(p, obs, cond, saved, dembeds, g, accumulate=False, side=None):
-    """Gradients of the ten encoder tensors into g."""
+    """Gradients of the ten (twelve with an fc) encoder tensors into g."""
     film, ys, hs = saved
     fk = _Fork(side)
     dfilm = torch.empty_like(film)
     packs = [None] + [ops.conv_up_pack(_ENC_L[l], p[2 * l]) for l in (1, 2, 3)]
-    dh = ops.relu_mask(dembeds.reshape(hs[3].shape).contiguous(), hs[3])
+    if len(p) > 10:   # fc: d h4 = (d embeds @ W) * relu'(h4) in the product's epilogue; its weight gradient on the fork
+        flat = hs[3].view(hs[3].shape[0], -1)
+        dh = ops.gemm(dembeds, p[8], epi=ops.EPI_MUL_DRELU, aux=flat).view(hs[3].shape)
+        fk.run(lambda: ops.gemm_wgrad(dembeds, flat, dW=g[8], db=g[9], accumulate=accumulate))
+    else:
+        dh = ops.relu_mask(dembeds.reshape(hs[3].shape).contiguous(), hs[3])
     dys = []   # every d y_l stays alive until fk.join(): the side stream's weight-gradient kernel of layer l still reads
     #            d y_l while this stream moves on, and a block freed here is handed to this stream's NEXT allocation
     #            (the caching allocator orders reuse on the allocating stream only)
@@ -81,7 +92,7 @@ def cond_encoder_bwd(p, obs, cond, saved, dembeds, g, accumulate=False, side=Non
                                                              accumulate=accumulate))
         if l > 0:
             dh = ops.conv_up(_ENC_L[l], dy, p[2 * l], None, epi=ops.EPI_MUL_DRELU, aux=hs[l - 1], pack=packs[l])
-    _film_grads(dfilm, cond, g[8], g[9], accumulate)
+    _film_grads(dfilm, cond, g[-2], g[-1], accumulate)
     fk.join()
     del dys
 
@@ -95,7 +106,7 @@ def _cond_decoder_trunk(p, feat, cond, head=None):
     film = _film(p[10], p[11], cond)
     pk2, pk3 = ops.conv_up_pack(ops.DEC2, p[4]), ops.conv_up_pack(ops.DEC3, p[6])
     w1 = p[2].view(p[2].shape[0], -1)
-    if _fused() and _dec_compose(rows):
+    if _fused() and _dec_compose(rows, p):
         # fc1 and conv1 composed (functional.dec_head_compose: linear in sequence, models/decoder.py:113-116): one bias per
         # output element, one FiLM pair per 25 of them (bias_div = -25)
         tabs = ops.film_tables(film, DEC_CHANNELS)
