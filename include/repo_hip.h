@@ -790,7 +790,9 @@ int repo_dual_step_tasks(int64_t C, float* log_beta, float* exp_avg, float* exp_
                          float* scalars_out, const unsigned* skip_if_nonzero, hipStream_t stream);
 
 /* dst[c * ldd + r] = src[r * lds + c] for r < rows, c < cols; columns [rows, ldd) of dst are written as zeros
- * (ldd - rows < 64; lds, ldd multiples of 4, 16-byte aligned pointers).  The host side uses it to hand the bf16x6 dense
+ * (ldd - rows < 64, else REPO_E_SHAPE; lds, ldd multiples of 4, 16-byte aligned pointers, else REPO_E_ALIGN).  The zeros
+ * hold for every accepted ldd, also where the pads lie beyond the last 64-row tile of src (rows = 64, ldd = 68): the
+ * launch covers ceil(ldd / 64) row tiles.  Nothing beyond cols rows of dst is written.  The host side uses it to hand the bf16x6 dense
  * engine (repo_gemm) k-contiguous operands for the decoder's E -> 3200 layer (E = config.embedding_size): forward on W^T (the reference's
  * ConvTranspose2d weight keeps its (in, out, kH, kW) layout: models/decoder.py:43), weight gradient on the transposed
  * activations -- torch's counterpart is the .t() view that at::mm resolves inside the BLAS call. */

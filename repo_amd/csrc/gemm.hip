@@ -516,7 +516,10 @@ extern "C" int repo_gemm(int transa, int transb, int64_t M, int64_t N, int64_t K
 }
 
 // dst[c][r] = src[r][c] (rows x cols -> cols x rows, ldd >= rows; columns [rows, ldd) of dst are written as zeros).
-// 64 x 64 tiles through LDS, 16-byte accesses on both sides.  Used to bring an operand of a big product into the
+// 64 x 64 tiles through LDS, 16-byte accesses on both sides.  The grid's row tiles cover dst's whole pitch,
+// ceil(ldd / 64) of them: a tile writes dst columns [r0, r0 + 64) below ldd, and whatever of them lies at or beyond `rows`
+// was loaded as zeros -- so the pads are written wherever they fall, in the last source tile or in one tile past it
+// (rows = 64, ldd = 68).  Used to bring an operand of a big product into the
 // k-contiguous form the bf16x6 engine runs fastest on (bgemm.h: NT 117 vs NN 153 us at 2450 x 3200 x 1024).
 namespace repo {
 __global__ __launch_bounds__(256) void transpose_kernel(int rows, int cols, const float* __restrict__ src, int lds_,
@@ -538,7 +541,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(int rows, int cols, cons
     for (int e = 0; e < 4; ++e) tile[ty + 16 * i][4 * tx + e] = v[e];
   }
   __syncthreads();
-  const bool last_rt = r0 + 64 >= rows;   // this tile also owns dst's pad columns [rows, ldd)
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = c0 + ty + 16 * i, r = r0 + 4 * tx;   // dst row c, columns r .. r+3
@@ -547,10 +549,10 @@ __global__ __launch_bounds__(256) void transpose_kernel(int rows, int cols, cons
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = tile[4 * tx + e][ty + 16 * i];   // zero beyond `rows` (loaded as zeros)
     float* d = dst + (size_t)c * ldd + r;
-    if (r + 3 < (last_rt ? ldd : rows)) *reinterpret_cast<f32x4*>(d) = v;
+    if (r + 3 < ldd) *reinterpret_cast<f32x4*>(d) = v;
     else
       for (int e = 0; e < 4; ++e)
-        if (r + e < (last_rt ? ldd : rows)) d[e] = v[e];
+        if (r + e < ldd) d[e] = v[e];
   }
 }
 }  // namespace repo
@@ -562,7 +564,7 @@ extern "C" int repo_transpose(int64_t rows, int64_t cols, const float* src, int6
   REPO_REQUIRE(rows * lds < kMaxIdx && cols * ldd < kMaxIdx, REPO_E_SHAPE);
   REPO_REQUIRE(src && dst, REPO_E_BADARG);
   REPO_REQUIRE(lds % 4 == 0 && ldd % 4 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0, REPO_E_ALIGN);
-  hipLaunchKernelGGL(repo::transpose_kernel, dim3((unsigned)((cols + 63) / 64), (unsigned)((rows + 63) / 64)), dim3(256), 0,
+  hipLaunchKernelGGL(repo::transpose_kernel, dim3((unsigned)((cols + 63) / 64), (unsigned)((ldd + 63) / 64)), dim3(256), 0,
                      stream, (int)rows, (int)cols, src, (int)lds, dst, (int)ldd);
   REPO_CHECK_LAUNCH();
   return REPO_OK;
