@@ -372,6 +372,18 @@ __global__ __launch_bounds__(512, 4) void mlp_bwd_kernel(MlpBwdArgs p) {
 // Instantiated for the reference heads: in_dim = belief + state = 230 (15 blocks), hidden = 200 (13), 4 or 5 layers,
 // out_dim <= 16 (reward / value: 1, actor: 2 A).  Other shapes run layer by layer through the GEMM engine.
 constexpr int kBI = 15, kBH = 13;
+
+// The same chains on 32-row tiles and the bf16 matrix pipe (mlp32.hip): mlp_fused_fwd / mlp_fused_bwd hand a call over
+// when mlp32_routed() says so (a row threshold per direction; never with repo_debug_rowtile32(0)).
+bool mlp32_routed(int64_t rows, bool reverse, const void* ws);
+size_t mlp32_ws_bytes(int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers);
+int mlp32_fwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int L, const float* x, int64_t ldx,
+              const float* const* params, float* const* hidden_out, float* out, int64_t ldo, void* ws,
+              hipStream_t stream, int act);
+int mlp32_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int L, const float* const* params,
+              const float* const* hidden_acts, const float* dout, int64_t lddout, float* const* dsave, float* dx,
+              int64_t lddx, int accumulate_dx, void* ws, hipStream_t stream, int act, const float* dout_w, int64_t rows_w);
+
 bool mlp_fused_ok(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int n_layers) {
   auto blk = [](int64_t k) { return pad16((int)k) >> 4; };
   return (n_layers == 4 || n_layers == 5) && blk(in_dim) == kBI && blk(hidden) == kBH && hidden % 4 == 0 &&
@@ -382,7 +394,8 @@ size_t mlp_fused_ws_floats(int64_t in_dim, int64_t hidden, int64_t out_dim, int 
   // forward and transposed packs have the same padded sizes up to the side that is padded; take the larger of each
   const size_t f = pack_floats(hidden, in_dim) + (n_layers - 2) * pack_floats(hidden, hidden) + pack_floats(out_dim, hidden);
   const size_t b = pack_floats(in_dim, hidden) + (n_layers - 2) * pack_floats(hidden, hidden) + pack_floats(hidden, out_dim);
-  return (f > b ? f : b) + 64;
+  const size_t f32 = (f > b ? f : b) + 64, b16 = (mlp32_ws_bytes(in_dim, hidden, out_dim, n_layers) + 3) / 4;  // either engine's packs
+  return f32 > b16 ? f32 : b16;
 }
 
 // two workgroups per CU fit (2 x 61 KB LDS, <= 128 VGPRs)
@@ -410,6 +423,8 @@ static int launch_fwd(const MlpFwdArgs& a, hipStream_t s) {
 int mlp_fused_fwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int L, const float* x, int64_t ldx,
                   const float* const* params, float* const* hidden_out, float* out, int64_t ldo, void* ws,
                   hipStream_t stream, int act) {
+  if (mlp32_routed(rows, false, ws))
+    return mlp32_fwd(rows, in_dim, hidden, out_dim, L, x, ldx, params, hidden_out, out, ldo, ws, stream, act);
   MlpFwdArgs a;
   a.trace = nullptr;
   a.rows = (int)rows, a.in_dim = (int)in_dim, a.hidden = (int)hidden, a.out_dim = (int)out_dim;
@@ -446,6 +461,9 @@ static int launch_bwd(const MlpBwdArgs& a, hipStream_t s) {
 int mlp_fused_bwd(int64_t rows, int64_t in_dim, int64_t hidden, int64_t out_dim, int L, const float* const* params,
                   const float* const* hidden_acts, const float* dout, int64_t lddout, float* const* dsave, float* dx,
                   int64_t lddx, int accumulate_dx, void* ws, hipStream_t stream, int act, const float* dout_w, int64_t rows_w) {
+  if (mlp32_routed(rows, true, ws))
+    return mlp32_bwd(rows, in_dim, hidden, out_dim, L, params, hidden_acts, dout, lddout, dsave, dx, lddx, accumulate_dx, ws,
+                     stream, act, dout_w, rows_w);
   MlpBwdArgs a;
   a.dout_w = dout_w, a.rows_w = (int)rows_w;
   a.rows = (int)rows, a.in_dim = (int)in_dim, a.hidden = (int)hidden, a.out_dim = (int)out_dim;
