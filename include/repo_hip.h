@@ -33,7 +33,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-#define REPO_ABI_VERSION 13
+#define REPO_ABI_VERSION 14
 
 #define REPO_OK 0
 #define REPO_E_BADARG (-1)
@@ -41,6 +41,7 @@ typedef struct ihipStream_t* hipStream_t;
 #define REPO_E_ALIGN (-3)
 #define REPO_E_WS_TOO_SMALL (-4)
 #define REPO_E_ARCH (-5)
+#define REPO_E_ENV (-6) /* an environment variable the library reads holds a value it does not know (repo_strerror names it) */
 
 /* epilogues of repo_gemm */
 #define REPO_EPI_NONE 0
@@ -119,6 +120,25 @@ int repo_debug_bconv(int enable);
 /* The same switch for the bf16x6 32-row-tile engines (csrc/rowtile32.h: the imagination rollout and the dense heads);
  * 0 = the 16-row fp32-MFMA engines of rowtile.h. */
 int repo_debug_rowtile32(int enable);
+
+/* ABI v14 -- convolution precision.  gfx950 has no TF32; the MFMA-bound convolutions run on the bf16 matrix pipe with every
+ * fp32 operand split into bf16 parts a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2) (round to nearest even):
+ *   REPO_CONV_PRECISION_HIGHEST (default)  the six products a_i b_j with i + j <= 4: fp32-accurate products;
+ *   REPO_CONV_PRECISION_HIGH               a1 b1 + a1 b2 + a2 b1: 16 significand bits per operand, half the MFMAs.  Per
+ *                                          output |error| <= 3 * 2^-16 * sum |a||b| (+ the fp32 accumulation both modes share);
+ *                                          against uint8 frames (exact in one bf16) x w1 + x w2 instead of x w1 + x w2 + x w3:
+ *                                          2^-16 * sum |x||w|.
+ * Inputs, outputs and accumulation are fp32 in both.  The mode selects an instantiation of the bf16 conv kernels behind
+ * repo_conv_down / repo_conv_up / repo_conv_wgrad / repo_decoder_out_nll and nothing else: the fp32-MFMA engines (and
+ * repo_debug_bconv(0), which selects them), repo_conv_up_nll, every dense product, the scans and the rollout do not read it;
+ * workspace sizes and weight packs do not depend on it (a pack written under one mode is valid under the other).
+ * repo_conv_precision sets the CALLING THREAD's mode and returns the previous one (thread-local like the repo_debug_* switches:
+ * see the note on autograd threads above); an unknown value changes nothing and returns REPO_E_BADARG.  A thread that never
+ * set it takes the process's environment variable REPO_CONV_PRECISION ("highest" | "high", read once; unset = highest); any
+ * other value there makes every conv entry point above, and this setter, return REPO_E_ENV. */
+#define REPO_CONV_PRECISION_HIGHEST 0
+#define REPO_CONV_PRECISION_HIGH 1
+int repo_conv_precision(int mode);
 
 /* ------------------------------------------------------------------ reparameterisation noise
  * The reference draws its noise from torch's global generator (torch.randn_like in models/rssm.py:49,61-63;

@@ -85,7 +85,7 @@ def lib():
         fn.argtypes = [_ctype(t) for t, _ in params]
         fn.restype = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64,
                       "constchar*": ctypes.c_char_p}[ret]
-    if L.repo_abi_version() != 13:
+    if L.repo_abi_version() != 14:
         raise RepoHipError("librepo_hip.so ABI version mismatch")
     _lib = L
     return L

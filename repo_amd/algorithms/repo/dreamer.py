@@ -17,6 +17,7 @@ row count so that a sum all-reduce of the flat gradient buffers (RCCL over xGMI)
 global-batch gradient before the global-norm clip, and every rank applies the identical
 Adam step.
 """
+import functools
 import glob
 import math
 import os
@@ -51,6 +52,19 @@ def _as_video(frames, fps):
     except (ImportError, AttributeError):  # no such module / a `common` package without a Video class
         from ...common.utils import Video
     return Video(frames, fps)
+
+
+def in_conv_precision(method):
+    """The agent method runs at the agent's convolution precision (config.conv_precision, ops.conv_precision): every path that
+    launches conv kernels -- train_dynamics, the acting step with its graph capture, _reconstruct -- goes through this one
+    wrapper.  A config without the key leaves the calling thread's setting alone (REPO_CONV_PRECISION, else "highest")."""
+    @functools.wraps(method)
+    def run(self, *args, **kwargs):
+        if not self._conv_precision_set:
+            return method(self, *args, **kwargs)
+        with ops.conv_precision(self._conv_precision):
+            return method(self, *args, **kwargs)
+    return run
 
 
 class Dreamer:
@@ -136,8 +150,19 @@ class Dreamer:
     # config.pixel_obs = False (state-vector observations: SymbolicEncoder / SymbolicObservationModel):
     # Dreamer and RePo.  FinetunedRePo, TIA and the multitask agents have encoders / decoders of their own: they refuse.
     _BUILDS_SYMBOLIC = True
+    # config.conv_precision = "high" (three-product bf16 convolutions): Dreamer and RePo, both frame sizes; with
+    # pixel_obs=False there is no conv and the key is ignored.  The other families refuse any value but "highest".
+    _BUILDS_CONV_PRECISION = True
 
     def build_models(self, config, env):
+        self._conv_precision = getattr(config, "conv_precision", "highest")
+        self._conv_precision_set = hasattr(config, "conv_precision")
+        if self._conv_precision not in ops.CONV_PRECISIONS:
+            raise ValueError(f'conv_precision={self._conv_precision!r}: expected "highest" or "high"')
+        if self._conv_precision != "highest" and not self._BUILDS_CONV_PRECISION:
+            raise NotImplementedError(
+                f"conv_precision={self._conv_precision!r}: {type(self).__name__} runs its convolutions at \"highest\" only; "
+                "the three-product mode is built and tested for Dreamer and RePo")
         self._symbolic = not config.pixel_obs
         if self._symbolic and not self._BUILDS_SYMBOLIC:
             raise NotImplementedError(
@@ -446,6 +471,7 @@ class Dreamer:
         assert obs.dtype in (torch.uint8, torch.float32), obs.dtype
         return obs, actions.float().contiguous(), rewards.float().contiguous(), nonterms.float().contiguous()
 
+    @in_conv_precision
     def train_dynamics(self, obs, actions, rewards, nonterms):
         """Dreamer world-model step (reference dreamer.py:241-302).  obs (L,B,3,64,64) float32 in
         [-1,1] (reference convention) or uint8 -- pixel_obs=False: (L,B,obs_size) float32; returns detached (beliefs,
@@ -845,6 +871,7 @@ class Dreamer:
             action = torch.clamp(action + torch.randn_like(action) * self.c.action_noise, -1, 1)
         return belief, posterior_state, action
 
+    @in_conv_precision
     def update_latent_and_select_action(self, belief, posterior_state, action, obs, explore=False):
         """One filtering step + policy (reference dreamer.py:175-196).
 
@@ -904,6 +931,7 @@ class Dreamer:
                     job()
             self.step += 1
 
+    @in_conv_precision
     def _reconstruct(self, belief, state):
         return self.obs_model(belief, state)
 

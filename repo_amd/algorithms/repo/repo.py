@@ -13,7 +13,7 @@ import torch
 
 from ... import functional as Fn
 from ... import ops
-from .dreamer import Dreamer
+from .dreamer import Dreamer, in_conv_precision
 from .models.utils import adam_param_group
 
 
@@ -117,6 +117,7 @@ class RePo(Dreamer):
                                grow)
         return self._latents_out(sv, actions, nonterms)
 
+    @in_conv_precision
     def train_dynamics(self, obs, actions, rewards, nonterms):
         c = self.c
         obs, actions, rewards, nonterms = self._prep_batch(obs, actions, rewards, nonterms)

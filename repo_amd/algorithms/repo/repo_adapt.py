@@ -44,6 +44,7 @@ from .repo import RePo
 
 class FinetunedRePo(RePo):
     _BUILDS_SYMBOLIC = False   # pixel_obs=False: train_encoder runs the conv encoder's passes (the reference pins uint8 frames)
+    _BUILDS_CONV_PRECISION = False   # conv_precision="high": built and tested for Dreamer and RePo
 
     def build_models(self, config, env):
         super().build_models(config, env)
@@ -155,6 +156,7 @@ class FinetunedRePo(RePo):
 
 class CalibratedRePo(RePo):
     _BUILDS_SYMBOLIC = False   # pixel_obs=False: the calibration frames are paired pixel frames (uint8, 6 channels)
+    _BUILDS_CONV_PRECISION = False   # conv_precision="high": built and tested for Dreamer and RePo
     _LOG_KEYS = ("f_loss_src", "f_loss_tgt", "f_kl", "aln_loss", "calib_loss", "encoder_loss")
     _LOG_KEYS_PAIR = ("dyn_loss",)
     _LOG_KEYS_SUPPORT = ("tau_loss", "tau_mean", "u_value")

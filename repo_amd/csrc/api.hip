@@ -2,7 +2,10 @@
 #include "common.h"
 
 #include <atomic>
+#include <stdlib.h>
 #include <string.h>
+
+#include <string>
 
 extern "C" int repo_abi_version(void) { return REPO_ABI_VERSION; }
 
@@ -52,6 +55,13 @@ extern "C" const char* repo_strerror(int code) {
     case REPO_E_ALIGN: return "misaligned pointer";
     case REPO_E_WS_TOO_SMALL: return "workspace too small";
     case REPO_E_ARCH: return "device is not gfx950";
+    case REPO_E_ENV: {   // the one variable the library reads (conv.hip); the text is built once
+      static const std::string msg = [] {
+        const char* e = getenv("REPO_CONV_PRECISION");
+        return std::string("environment variable REPO_CONV_PRECISION=\"") + (e ? e : "") + "\": expected \"highest\" or \"high\"";
+      }();
+      return msg.c_str();
+    }
     default: break;
   }
   if (code > 0) return hipGetErrorString((hipError_t)code);

@@ -113,12 +113,17 @@ __global__ __launch_bounds__(256) void bconv_pack_kernel(BPackArgs p) {
   }
 }
 
-template <class G, class T, class BigT = float>
+// NPROD, the products per block (repo_conv_precision): float frames 6 ("highest") or 3 ("high": a1 b1 + a1 b2 + a2 b1, planes
+// 1 and 2 of the patch and of the pack); uint8 frames 3 (x w1 + x w2 + x w3) or 2 (x w1 + x w2).  The planes an instantiation
+// does not multiply are neither split, stored nor copied; the LDS layout is the same in all four.
+template <class G, class T, class BigT = float, int NPROD = 6>
 __global__ __launch_bounds__(T::NT) void bconv_down_kernel(DownArgs p) {
   typedef BGeo<G> BG;
   typedef BPack<G, T> P;
   constexpr bool U8 = std::is_same<BigT, uint8_t>::value;   // raw bytes: ONE patch plane (a byte is exact in bf16)
-  constexpr int NPL = U8 ? 1 : 3;
+  static_assert(U8 ? (NPROD == 3 || NPROD == 2) : (NPROD == 6 || NPROD == 3), "products per block");
+  constexpr int NWPL = U8 ? NPROD : BgProd<U8 ? 6 : NPROD>::PLANES;   // weight planes read
+  constexpr int NPL = U8 ? 1 : NWPL;
   static_assert(BG::CBP == G::CB || P::NSL == 1, "a padded channel count: one chunk (the phantom channel is chunk-local)");
   static_assert(!U8 || !BG::ODD, "uint8 frames: even row pitch");
   constexpr bool ODD = BG::ODD;
@@ -146,10 +151,10 @@ __global__ __launch_bounds__(T::NT) void bconv_down_kernel(DownArgs p) {
   constexpr bool QROW = ODD;
   static_assert(!ODD || WBE % 4 == 0, "padded pitch: whole quads per row");
   constexpr int PLV_E = PLMAX_E / 4;
-  constexpr int W_NV = 3 * NBLK * 2 * BM;                    // 16-byte weight vectors per chunk
+  constexpr int W_NV = NWPL * NBLK * 2 * BM;                 // 16-byte weight vectors per chunk (the planes come first to last)
   constexpr int W_PER = (W_NV + NT - 1) / NT, P_PER = (CK * (QROW ? PLV_E : PLV) + NT - 1) / NT;
   constexpr int EPI_FLOATS = (NT / 64) * 32 * 36 + (NT / 64) * TM * 32;
-  constexpr int LDS_BYTES = cmax(3 * WPLANE + NPL * PPLANE + 64, 4 * EPI_FLOATS);
+  constexpr int LDS_BYTES = cmax(3 * WPLANE + (U8 ? 1 : 3) * PPLANE + 64, 4 * EPI_FLOATS);
   __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
   char* Wl = lds;
   char* Pl = lds + 3 * WPLANE;
@@ -269,7 +274,7 @@ __global__ __launch_bounds__(T::NT) void bconv_down_kernel(DownArgs p) {
           bg_split3(rpv[j][2], rpv[j][3], b1, b2, b3);
           *reinterpret_cast<bg_u32x2*>(Pl + plds[j]) = bg_u32x2{a1, b1};
           *reinterpret_cast<bg_u32x2*>(Pl + PPLANE + plds[j]) = bg_u32x2{a2, b2};
-          *reinterpret_cast<bg_u32x2*>(Pl + 2 * PPLANE + plds[j]) = bg_u32x2{a3, b3};
+          if constexpr (NPL > 2) *reinterpret_cast<bg_u32x2*>(Pl + 2 * PPLANE + plds[j]) = bg_u32x2{a3, b3};
         }
       }
   };
@@ -284,7 +289,7 @@ __global__ __launch_bounds__(T::NT) void bconv_down_kernel(DownArgs p) {
       const int g = blk / BG::BPG, b = blk % BG::BPG;
       bg_bf16x8 fa[TM][3], fb[TN][NPL];
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
+      for (int pl = 0; pl < NWPL; ++pl) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
           fa[i][pl] = *reinterpret_cast<const bg_bf16x8*>(Wl + pl * WPLANE + blk * (2 * BM * 16) + abase + i * 32 * 16);
@@ -303,7 +308,11 @@ __global__ __launch_bounds__(T::NT) void bconv_down_kernel(DownArgs p) {
         for (int j = 0; j < TN; ++j) {
           f32x16 c = acc[i][j];  // smallest terms first
           if constexpr (U8) {   // the byte plane is exact: w = w1 + w2 + w3 against it
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], c, 0, 0, 0);
+            if constexpr (NPROD == 3) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], c, 0, 0, 0);
+          } else if constexpr (NPROD == 3) {
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][1], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], c, 0, 0, 0);
           } else {
@@ -344,7 +353,7 @@ __global__ __launch_bounds__(T::NT) void bconv_down_kernel(DownArgs p) {
   dconv_down_epilogue<G, T>(p, reinterpret_cast<float*>(lds), acc, n0, m0, Ntot);
 }
 
-template <class G, class T, class BigT = float>
+template <class G, class T, class BigT = float, int NPROD = 6>
 inline int launch_bconv_down(const DownArgs& a, const float* w, char* pack, hipStream_t s) {
   typedef BPack<G, T> P;
   constexpr bool U8 = std::is_same<BigT, uint8_t>::value;
@@ -357,7 +366,7 @@ inline int launch_bconv_down(const DownArgs& a, const float* w, char* pack, hipS
   b.w_bytes = (unsigned)P::BYTES;
   if (U8) b.bias = reinterpret_cast<const float*>(pack + P::BYTES);   // the folded bias: b - sum w (pack kernel)
   const long gx = ((long)a.nimg * G::PS + T::BN - 1) / T::BN, gy = P::MT;
-  hipLaunchKernelGGL((bconv_down_kernel<G, T, BigT>), dim3((unsigned)gx, (unsigned)gy), dim3(T::NT), 0, s, b);
+  hipLaunchKernelGGL((bconv_down_kernel<G, T, BigT, NPROD>), dim3((unsigned)gx, (unsigned)gy), dim3(T::NT), 0, s, b);
   e = hipGetLastError();
   return e == hipSuccess ? REPO_OK : (int)e;
 }

@@ -24,8 +24,11 @@
 
 namespace repo {
 
-template <class TgtT>
+// NPROD (bgemm.h, BgProd): 6 products per tap and pixel tile, or 3 ("high": a1 b1 + a1 b2 + a2 b1) -- then the weights' third
+// plane is neither written to LDS nor read, and the patch's third plane is neither split, stored nor read.
+template <class TgtT, int NPROD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void bdec4_nll_kernel(NllArgs p) {
+  constexpr int NPLN = BgProd<NPROD>::PLANES;
   constexpr int CS = 32, HS = 30, PS = 900, HB = 64;
   constexpr int PC = 35;                        // columns x = -2 .. 31 of a patch row (+1: an odd pitch, see the staging)
   constexpr int PLB = 10 * 4 * PC * 16;         // bytes per bf16 plane: [row 10][octet 4][column 35][8 channels]
@@ -63,7 +66,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void b
       }
       wa[tap][0] = __builtin_bit_cast(bg_bf16x8, q1);
       wa[tap][1] = __builtin_bit_cast(bg_bf16x8, q2);
-      if (wv == 0) *reinterpret_cast<u32x4s*>(wlo + (tap * 64 + lane) * 16) = q3;
+      if constexpr (NPLN > 2)
+        if (wv == 0) *reinterpret_cast<u32x4s*>(wlo + (tap * 64 + lane) * 16) = q3;
     }
   }
   // zero borders (columns -2, -1, 30, 31) are never written again
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void b
           char* dst = lds + plds[j] + e * 16 + ((e >= 2 && x0 == 28) ? ROWSTEP : 0);
           *reinterpret_cast<bg_u32x2*>(dst) = bg_u32x2{a1, b1};
           *reinterpret_cast<bg_u32x2*>(dst + PLB) = bg_u32x2{a2, b2};
-          *reinterpret_cast<bg_u32x2*>(dst + 2 * PLB) = bg_u32x2{a3, b3};
+          if constexpr (NPLN > 2) *reinterpret_cast<bg_u32x2*>(dst + 2 * PLB) = bg_u32x2{a3, b3};
         }
       }
   };
@@ -167,23 +171,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void b
     for (int t = 0; t < 4; ++t) acc[t] = f32x4acc{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
-      const bg_bf16x8 wa3 = *reinterpret_cast<const bg_bf16x8*>(wlo + (tap * 64 + lane) * 16);
+      bg_bf16x8 wa3 = wa[tap][0];   // (unused with three products)
+      if constexpr (NPLN > 2) wa3 = *reinterpret_cast<const bg_bf16x8*>(wlo + (tap * 64 + lane) * 16);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {   // two pixel tiles at a time: their MFMA chains interleave, 24 fragment registers
         bg_bf16x8 fb[2][3];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-          for (int pl = 0; pl < 3; ++pl)
+          for (int pl = 0; pl < NPLN; ++pl)
             fb[t][pl] = *reinterpret_cast<const bg_bf16x8*>(lds + pl * PLB + bbase[2 * h + t] + ((tap / 3) * 4 * PC + tap % 3) * 16);
         f32x4acc c0 = acc[2 * h], c1 = acc[2 * h + 1];   // smallest terms first
 #ifndef BD4_NO_MFMA
-        c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][1], fb[0][1], c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][1], fb[1][1], c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][0], fb[0][2], c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][0], fb[1][2], c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa3, fb[0][0], c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa3, fb[1][0], c1, 0, 0, 0);
+        if constexpr (NPROD == 6) {
+          c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][1], fb[0][1], c0, 0, 0, 0);
+          c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][1], fb[1][1], c1, 0, 0, 0);
+          c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][0], fb[0][2], c0, 0, 0, 0);
+          c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][0], fb[1][2], c1, 0, 0, 0);
+          c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa3, fb[0][0], c0, 0, 0, 0);
+          c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa3, fb[1][0], c1, 0, 0, 0);
+        }
         c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][0], fb[0][1], c0, 0, 0, 0);
         c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][0], fb[1][1], c1, 0, 0, 0);
         c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][1], fb[0][0], c0, 0, 0, 0);
@@ -191,8 +198,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void b
         c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][0], fb[0][0], c0, 0, 0, 0);
         c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[tap][0], fb[1][0], c1, 0, 0, 0);
 #else
-        c0[0] += (float)fb[0][0][0] + (float)fb[0][1][0] + (float)fb[0][2][0] + (float)wa3[0];
-        c1[0] += (float)fb[1][0][0] + (float)fb[1][1][0] + (float)fb[1][2][0];
+        c0[0] += (float)fb[0][0][0] + (float)fb[0][1][0] + (float)fb[0][NPLN - 1][0] + (float)wa3[0];
+        c1[0] += (float)fb[1][0][0] + (float)fb[1][1][0] + (float)fb[1][NPLN - 1][0];
 #endif
         acc[2 * h] = c0, acc[2 * h + 1] = c1;
       }

@@ -47,6 +47,17 @@ __device__ __forceinline__ void bg_split3(float x0, float x1, unsigned& p1, unsi
   p3 = __builtin_bit_cast(unsigned, __builtin_convertvector(bg_f32x2{s0, s1}, bg_bf16x2));
 }
 
+// Convolution precision (conv.hip, repo_conv_precision): how many of the six products a conv kernel forms, a template
+// argument of every bf16 conv engine.  The product lists of those kernels -- planes {1, 0, 2, 0, 1, 0} of one operand against
+// {1, 2, 0, 1, 0, 0} of the other, smallest terms first -- END with a1 b2, a2 b1, a1 b1: NPROD = 3 ("high") is their last three,
+// 16 significand bits per operand, and the third plane of either operand is never read.
+template <int NPROD>
+struct BgProd {
+  static_assert(NPROD == 6 || NPROD == 3, "six products (i + j <= 4) or three (a1 b1 + a1 b2 + a2 b1)");
+  static constexpr int FIRST = 6 - NPROD;            // first entry of the six-product list this instantiation forms
+  static constexpr int PLANES = NPROD == 6 ? 3 : 2;  // planes of an operand it reads
+};
+
 struct BgArgs {
   Dense2D A, B;  // A: [M][K] if A_KC else [K][M];  B: [N][K] if B_KC else [K][N]
   DenseEpi e;

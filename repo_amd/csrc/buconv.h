@@ -141,14 +141,18 @@ __device__ __forceinline__ void buconv_split(const float (&raw)[C::KST], BFrag (
 // JX; for even kernels every class has all J x J taps and (0, 0) serves them all -- the class itself, `cls`, only enters
 // addresses).  A0 = the weight buffer the chunk's FIRST tap sits in: the taps alternate between the two buffers, the
 // next chunk (same tiles' next K-slice, or the next tiles) starts where this one ends.
-template <class G, class C, int PY, int PX, int NTL, int NEXT_NTL, int A0>
+// NPROD (bgemm.h, BgProd): the chain of a (tile, tap) is NPROD KB MFMAs -- 6 per k-block, or the list's last 3 ("high"): then no
+// third-plane weight fragment is loaded and the third plane of the tiles (split in registers) is never formed.  The LDS
+// read-modify-write of the planes rides the same slots of the chain in both (a chain has at least six slots).
+template <class G, class C, int PY, int PX, int NTL, int NEXT_NTL, int A0, int NPROD>
 __device__ __forceinline__ void buconv_chunk(const UScatArgs& p, char* pl, int cls, int lane, const BUChunk& d,
                                              const BUChunk& nx, int dummy_ofs, BFrag (&bfr)[C::NC][C::KB],
                                              float (&raw)[C::NC][C::KST], BFrag (&afr)[2][C::KB]) {
   constexpr int KB = C::KB, J = C::J, NXM = C::NXM, PLANE = C::PLANE;
   constexpr int JY = (G::KS - PY + 1) / 2, JX = (G::KS - PX + 1) / 2, NTAP = JY * JX;
   constexpr int NP = (NTL + 1) / 2;
-  constexpr int SLOTS = 6 * KB;
+  constexpr int SLOTS = NPROD * KB;
+  static_assert(SLOTS >= 6, "slots 1, 2, 4, 5 of a chain carry the planes' loads and stores");
   const int lp = lane & 15, lq = lane >> 4;
   const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.wp, p.wp_bytes);
   const unsigned a_lane = 16u * (unsigned)lane;
@@ -158,7 +162,7 @@ __device__ __forceinline__ void buconv_chunk(const UScatArgs& p, char* pl, int c
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
-      for (int q = 0; q < 3; ++q)
+      for (int q = 0; q < BgProd<NPROD>::PLANES; ++q)
         a[kb][q] = __builtin_bit_cast(bg_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
             rw, a_lane + 1024u * (unsigned)q, sbase + (unsigned)tn * C::TAP_BYTES + 3072u * (unsigned)kb, 0));
   };
@@ -200,7 +204,7 @@ __device__ __forceinline__ void buconv_chunk(const UScatArgs& p, char* pl, int c
       for (int s = 0; s < SLOTS; ++s) {
         // slot s = (kb, term): smallest terms first inside a k-block
         constexpr int TA[6] = {1, 0, 2, 0, 1, 0}, TB[6] = {1, 2, 0, 1, 0, 0};
-        const int kb = s / 6, ta = TA[s % 6], tb = TB[s % 6];
+        const int kb = s / NPROD, ta = TA[BgProd<NPROD>::FIRST + s % NPROD], tb = TB[BgProd<NPROD>::FIRST + s % NPROD];
         ca0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[ab][kb][ta], bfr[j0][kb][tb], ca0, 0, 0, 0);
         if (two) ca1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[ab][kb][ta], bfr[j1][kb][tb], ca1, 0, 0, 0);
         if (have_prev) {
@@ -235,7 +239,7 @@ __device__ __forceinline__ void buconv_chunk(const UScatArgs& p, char* pl, int c
 
 // The chunks of one workgroup tile in order: for each K-slice, the tile chunks (NFULL of NC tiles + a tail).  Chunk c
 // is instantiated with its own tile count, its successor's, and the weight-buffer parity it starts in.
-template <class G, class C, int PY, int PX, int CI>
+template <class G, class C, int PY, int PX, int CI, int NPROD>
 __device__ __forceinline__ void buconv_run(const UScatArgs& p, char* buf, int cls, int lane, int img0, int grp,
                                            BFrag (&bfr)[C::NC][C::KB], float (&raw)[C::NC][C::KST], BFrag (&afr)[2][C::KB]) {
   constexpr int NC = C::NC, NT = C::NT;
@@ -249,12 +253,12 @@ __device__ __forceinline__ void buconv_run(const UScatArgs& p, char* buf, int cl
     constexpr int NEXT = more ? (nct < NFULL ? NC : NTAIL) : 1;
     const BUChunk d{img0, grp, ct * NC, ks, true};
     const BUChunk nx{img0, grp, nct * NC, nks, more};
-    buconv_chunk<G, C, PY, PX, NTL, NEXT, (CI * NTAP) & 1>(p, buf, cls, lane, d, nx, 4 * C::LDS_FLOATS, bfr, raw, afr);
-    buconv_run<G, C, PY, PX, CI + 1>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
+    buconv_chunk<G, C, PY, PX, NTL, NEXT, (CI * NTAP) & 1, NPROD>(p, buf, cls, lane, d, nx, 4 * C::LDS_FLOATS, bfr, raw, afr);
+    buconv_run<G, C, PY, PX, CI + 1, NPROD>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
   }
 }
 
-template <class G, class C>
+template <class G, class C, int NPROD>
 __global__ __launch_bounds__(256, 2) void buconv_scatter_kernel(UScatArgs p) {
   constexpr int GI = C::GI, NC = C::NC, NT = C::NT, JJ = C::J * C::J;
   constexpr int FIRST_NTL = NT / NC > 0 ? NC : NT % NC;
@@ -276,7 +280,7 @@ __global__ __launch_bounds__(256, 2) void buconv_scatter_kernel(UScatArgs p) {
 #pragma unroll
     for (int kb = 0; kb < C::KB; ++kb)
 #pragma unroll
-      for (int q = 0; q < 3; ++q)
+      for (int q = 0; q < BgProd<NPROD>::PLANES; ++q)
         afr[0][kb][q] = __builtin_bit_cast(bg_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
             rw, 16u * (unsigned)lane + 1024u * (unsigned)q,
             (unsigned)(((grp * 4 + cls) * C::KSL) * JJ) * (unsigned)C::TAP_BYTES + 3072u * (unsigned)kb, 0));
@@ -286,12 +290,12 @@ __global__ __launch_bounds__(256, 2) void buconv_scatter_kernel(UScatArgs p) {
 
   char* buf = reinterpret_cast<char*>(planes);
   if constexpr (G::KS % 2 == 0) {
-    buconv_run<G, C, 0, 0, 0>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
+    buconv_run<G, C, 0, 0, 0, NPROD>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
   } else {  // odd kernels: the class's tap set is a compile-time property of its own instantiation
-    if (cls == 0) buconv_run<G, C, 0, 0, 0>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
-    else if (cls == 1) buconv_run<G, C, 0, 1, 0>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
-    else if (cls == 2) buconv_run<G, C, 1, 0, 0>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
-    else buconv_run<G, C, 1, 1, 0>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
+    if (cls == 0) buconv_run<G, C, 0, 0, 0, NPROD>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
+    else if (cls == 1) buconv_run<G, C, 0, 1, 0, NPROD>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
+    else if (cls == 2) buconv_run<G, C, 1, 0, 0, NPROD>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
+    else buconv_run<G, C, 1, 1, 0, NPROD>(p, buf, cls, lane, img0, grp, bfr, raw, afr);
   }
   __syncthreads();
   if (G::PB % 4 == 0) uconv_drain<G, C>(p, planes, grp, img0, cls, lane);
@@ -307,7 +311,7 @@ inline int launch_buconv_pack(const float* w, void* ws, size_t ws_bytes, hipStre
   return e == hipSuccess ? REPO_OK : (int)e;
 }
 
-template <class G, class C>
+template <class G, class C, int NPROD>
 inline int launch_buconv_scatter(const float* small, const float* w, const float* bias, const float* aux, float* out,
                                  int64_t nimg, int epi, int packed, void* ws, size_t ws_bytes, hipStream_t s) {
   if (!ws || ws_bytes < C::PACK_BYTES) return REPO_E_WS_TOO_SMALL;
@@ -320,9 +324,9 @@ inline int launch_buconv_scatter(const float* small, const float* w, const float
               (unsigned)C::PACK_BYTES};
   constexpr int lds_b = C::LDS_TOTAL_FLOATS * (int)sizeof(float);
   static_assert(lds_b <= 80 * 1024, "two workgroups per CU");
-  hipError_t e = hipFuncSetAttribute((const void*)buconv_scatter_kernel<G, C>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);
+  hipError_t e = hipFuncSetAttribute((const void*)buconv_scatter_kernel<G, C, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((buconv_scatter_kernel<G, C>), dim3((unsigned)(ngi * C::NGRP)), dim3(256), lds_b, s, a);
+  hipLaunchKernelGGL((buconv_scatter_kernel<G, C, NPROD>), dim3((unsigned)(ngi * C::NGRP)), dim3(256), lds_b, s, a);
   e = hipGetLastError();
   return e == hipSuccess ? REPO_OK : (int)e;
 }

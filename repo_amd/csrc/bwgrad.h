@@ -27,8 +27,12 @@ constexpr int bw_pitch(int len) {  // >= len, == 8 (mod 16) bf16 elements
   return p + 8;
 }
 
-template <class G, class T>
+// NPROD (bgemm.h, BgProd): 6 products per block and tile, or the list's last 3 ("high") -- then no third-plane fragment of `small`
+// is read and the third plane of `big` (split in registers) is never formed.  All three planes of `small` are staged in either
+// case: the bias gradient sums them (a = a1 + a2 + a3 exactly).
+template <class G, class T, int NPROD>
 __global__ __launch_bounds__(T::NT) void bconv_wgrad_kernel(WgradArgs p) {
+  constexpr int NPLN = BgProd<NPROD>::PLANES;
   constexpr int BM = T::BM, BN = T::BN, TM = T::TM, TN = T::TN, NT = T::NT, GI = T::GI, RB = T::RB;
   constexpr int NW = G::CB * G::KK;
   constexpr int NB = (G::HS + RB - 1) / RB;
@@ -168,7 +172,7 @@ __global__ __launch_bounds__(T::NT) void bconv_wgrad_kernel(WgradArgs p) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int q = 0; q < 3; ++q)
+          for (int q = 0; q < NPLN; ++q)
             fa[i][q] = *reinterpret_cast<const bg_bf16x8*>(ar + q * APLANE + abase[i] + 32 * b);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -188,16 +192,18 @@ __global__ __launch_bounds__(T::NT) void bconv_wgrad_kernel(WgradArgs p) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) bg_split3(v[2 * e], v[2 * e + 1], pl[0][e], pl[1][e], pl[2][e]);
 #pragma unroll
-          for (int q = 0; q < 3; ++q) fb[j][q] = __builtin_bit_cast(bg_bf16x8, u32x4s{pl[q][0], pl[q][1], pl[q][2], pl[q][3]});
+          for (int q = 0; q < NPLN; ++q) fb[j][q] = __builtin_bit_cast(bg_bf16x8, u32x4s{pl[q][0], pl[q][1], pl[q][2], pl[q][3]});
         }
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int j = 0; j < TN; ++j) {
             f32x16 cacc = acc[i][j];  // smallest terms first
-            cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][1], cacc, 0, 0, 0);
-            cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][2], cacc, 0, 0, 0);
-            cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], cacc, 0, 0, 0);
+            if constexpr (NPROD == 6) {
+              cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][1], cacc, 0, 0, 0);
+              cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][2], cacc, 0, 0, 0);
+              cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], cacc, 0, 0, 0);
+            }
             cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][1], cacc, 0, 0, 0);
             cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], cacc, 0, 0, 0);
             cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], cacc, 0, 0, 0);
@@ -271,11 +277,11 @@ __global__ __launch_bounds__(T::NT) void bconv_wgrad_kernel(WgradArgs p) {
   }
 }
 
-template <class G, class T>
+template <class G, class T, int NPROD>
 inline int launch_bconv_wgrad(const WgradArgs& a, int splits, hipStream_t s) {
   constexpr int NW = G::CB * G::KK;
   dim3 grid((NW + T::BN - 1) / T::BN, (G::CS + T::BM - 1) / T::BM, (unsigned)splits);
-  hipLaunchKernelGGL((bconv_wgrad_kernel<G, T>), grid, dim3(T::NT), 0, s, a);
+  hipLaunchKernelGGL((bconv_wgrad_kernel<G, T, NPROD>), grid, dim3(T::NT), 0, s, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? REPO_OK : (int)e;
 }

@@ -10,6 +10,7 @@
 //   wgrad: dw[cs][cb][ky][kx] = sum_{img,sy,sx} small[img][cs][sy][sx] big[img][cb][2sy+ky][2sx+kx]
 //          (+ the bias gradient of `small`), split over images into slabs, reduced in fixed order
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <type_traits>
@@ -31,6 +32,26 @@ namespace repo {
 // Test aid (repo_debug_bconv): 0 keeps every conv layer on the fp32-MFMA kernels.  Thread-local (api.hip): the setting
 // of the calling host thread, read at launch time.
 static thread_local int t_bconv_enabled = 1;
+
+// Convolution precision (repo_conv_precision): REPO_CONV_PRECISION_HIGHEST forms the six products of the three-way bf16 split,
+// REPO_CONV_PRECISION_HIGH the three of a two-way split (bgemm.h, BgProd).  Thread-local like the switch above; a thread that has
+// not set it takes the process's REPO_CONV_PRECISION (read once).  An unknown name there is an error of every conv entry point
+// (REPO_E_ENV), not a fall-back.  Read by the three plans and the repo_decoder_out_nll decision, by nothing else.
+static thread_local int t_conv_precision = -1;
+static int env_conv_precision() {
+  static const int mode = [] {
+    const char* e = getenv("REPO_CONV_PRECISION");
+    if (!e || !*e || !strcmp(e, "highest")) return REPO_CONV_PRECISION_HIGHEST;
+    return !strcmp(e, "high") ? REPO_CONV_PRECISION_HIGH : REPO_E_ENV;
+  }();
+  return mode;
+}
+static int conv_precision() { return t_conv_precision >= 0 ? t_conv_precision : env_conv_precision(); }
+static bool conv_precision_high() { return conv_precision() == REPO_CONV_PRECISION_HIGH; }
+#define REPO_CONV_PRECISION_GUARD() \
+  do {                              \
+    if (conv_precision() < 0) return REPO_E_ENV; \
+  } while (0)
 
 template <int CB_, int CS_, int HB_, int KS_>
 struct Geo {
@@ -551,6 +572,7 @@ struct DownPlan {
   long tiles;          // pixel tiles of the engine's grid = rows of the channel-sum partials (repo_conv_down's dbias)
   size_t pack_bytes;   // the weight pack at the head of the workspace = offset of the partials
   size_t parts_bytes;  // 0 unless the channel sums are wanted
+  bool high;           // repo_conv_precision: the bf16 engines' three-product instantiation (two against uint8 frames)
   size_t need() const { return pack_bytes + parts_bytes; }
 };
 template <class G, class BigT>
@@ -560,7 +582,7 @@ static DownPlan down_plan(int64_t nimg, int epi, bool has_bias, bool wants_dbias
   const long px = nimg * (long)G::PS;
   auto plan = [&](DownEngine e, long bn, size_t pack) {
     const long tiles = (px + bn - 1) / bn;
-    return DownPlan{e, tiles, pack, wants_dbias ? (size_t)tiles * G::CS * sizeof(float) : 0};
+    return DownPlan{e, tiles, pack, wants_dbias ? (size_t)tiles * G::CS * sizeof(float) : 0, conv_precision_high()};
   };
   if constexpr (kOn<BT>) {
     if (t_bconv_enabled && px > 512) {
@@ -600,10 +622,16 @@ static int conv_down_t(int64_t nimg, const BigT* big, const float* w, const floa
   int rc = REPO_E_BADARG;
   switch (p.engine) {
     case DownEngine::Tcd:
-      if constexpr (kOn<typename Route<G>::DownTcd>) rc = launch_tconv_down<typename Route<G>::DownTcd>(a, w, (char*)ws, s);
+      if constexpr (kOn<typename Route<G>::DownTcd>)
+        rc = p.high ? launch_tconv_down<typename Route<G>::DownTcd, 3>(a, w, (char*)ws, s)
+                    : launch_tconv_down<typename Route<G>::DownTcd, 6>(a, w, (char*)ws, s);
       break;
     case DownEngine::Bf16:
-      if constexpr (kOn<DownBfTile<G, BigT>>) rc = launch_bconv_down<G, DownBfTile<G, BigT>, BigT>(a, w, (char*)ws, s);
+      if constexpr (kOn<DownBfTile<G, BigT>>) {
+        constexpr int NFULL = std::is_same<BigT, float>::value ? 6 : 3;   // uint8 frames are exact in one bf16
+        rc = p.high ? launch_bconv_down<G, DownBfTile<G, BigT>, BigT, NFULL == 6 ? 3 : 2>(a, w, (char*)ws, s)
+                    : launch_bconv_down<G, DownBfTile<G, BigT>, BigT, NFULL>(a, w, (char*)ws, s);
+      }
       break;
     case DownEngine::Fp32Lat: rc = launch_dconv_down<G, BigT, DownLatTile<G>>(a, s); break;
     case DownEngine::Fp32: rc = launch_dconv_down<G, BigT, typename Route<G>::Down>(a, s); break;
@@ -625,6 +653,7 @@ struct UpPlan {
   size_t tcu_off;    // ... at this offset
   size_t need;       // bytes this call's engine reads
   size_t total;      // bytes of the layer's packs together (repo_conv_up_workspace_bytes)
+  bool high;         // repo_conv_precision: the bf16 engines' three-product instantiation (the packs are the same)
 };
 template <class G>
 static UpPlan up_plan(int64_t nimg, int epi, size_t ws_have) {
@@ -634,7 +663,7 @@ static UpPlan up_plan(int64_t nimg, int epi, size_t ws_have) {
   static_assert(!kOn<BC> || kOn<UC>, "the bf16x6 scatter kernel has an fp32 twin (repo_debug_bconv(0))");
   static_assert(!kOn<typename R::DirectUp> || !kOn<UC>, "the direct kernel or the scatter kernels");
   static_assert(!R::UpTconv || kOn<BC>, "the gather-form kernel follows the debug switch of the bf16x6 kernels");
-  UpPlan p{UpEngine::Merged, UpEngine::Merged, false, 0, 0, 0};
+  UpPlan p{UpEngine::Merged, UpEngine::Merged, false, 0, 0, 0, conv_precision_high()};
   size_t room = 0;
   if constexpr (kOn<BC>) {
     p.base = t_bconv_enabled ? UpEngine::BfScatter : UpEngine::Scatter;
@@ -689,11 +718,13 @@ static int conv_up_t(int64_t nimg, const float* small, const float* w, const flo
       char* pack = (char*)ws + p.tcu_off;
       if (!packed)
         if (const int rc = launch_tconv_up_pack(w, pack, s)) return rc;
-      return launch_tconv_up(small, pack, bias, aux, big, nimg, epi, s);
+      return p.high ? launch_tconv_up<3>(small, pack, bias, aux, big, nimg, epi, s)
+                    : launch_tconv_up<6>(small, pack, bias, aux, big, nimg, epi, s);
     }
   if constexpr (kOn<typename R::UpBfScatter>)
     if (p.engine == UpEngine::BfScatter)
-      return launch_buconv_scatter<G, typename R::UpBfScatter>(small, w, bias, aux, big, nimg, epi, packed, ws, ws_bytes, s);
+      return p.high ? launch_buconv_scatter<G, typename R::UpBfScatter, 3>(small, w, bias, aux, big, nimg, epi, packed, ws, ws_bytes, s)
+                    : launch_buconv_scatter<G, typename R::UpBfScatter, 6>(small, w, bias, aux, big, nimg, epi, packed, ws, ws_bytes, s);
   if constexpr (kOn<typename R::DirectUp>) {
     return launch_dconv_up<G, typename R::DirectUp>(small, w, bias, aux, big, nimg, epi, packed, ws, ws_bytes, s);
   } else if constexpr (kOn<typename R::UpScatter>) {
@@ -742,6 +773,7 @@ struct WgradPlan {
   bool wave_reduce;     // conv_slab_reduce_wave_kernel (many splits, few outputs) or conv_slab_reduce_kernel
   size_t chan_off;      // offset of the separate channel-sum pass's partials
   size_t need;
+  bool high;            // repo_conv_precision: the bf16 engines' three-product instantiation
 };
 template <class G, class BigT>
 static WgradPlan wgrad_plan(int64_t nimg, bool wants_dbig) {
@@ -753,7 +785,7 @@ static WgradPlan wgrad_plan(int64_t nimg, bool wants_dbig) {
   const long min_ips = T::GI * ((G::PS >= 512) ? 1 : (G::PS >= 64 ? 2 : 4));
   const long ips = (std::max((long)(nimg + want - 1) / want, min_ips) + T::GI - 1) / T::GI * T::GI;
   constexpr int row = G::CS * (G::CB * G::KK + 1);
-  WgradPlan p{WgradEngine::Fp32, (int)ips, (int)((nimg + ips - 1) / ips), row, false, false, 0, 0};
+  WgradPlan p{WgradEngine::Fp32, (int)ips, (int)((nimg + ips - 1) / ips), row, false, false, 0, 0, conv_precision_high()};
   p.wave_reduce = p.splits >= 64 && row <= 65536;
   size_t slabs = (size_t)p.splits * row * sizeof(float);
   if constexpr (kOn<typename R::WgradBf> && kFloat) {
@@ -767,7 +799,7 @@ static WgradPlan wgrad_plan(int64_t nimg, bool wants_dbig) {
     // where the taps reach every row and column of `big` (decoder conv3; not the 31 x 31 planes of encoder conv2, whose
     // last row and column no window touches) every element is staged exactly once and its channel sums ride along
     constexpr bool covers = R::TwDbig && G::HB == 2 * (G::HS - 1) + G::KS;
-    if (kFloat && t_bconv_enabled) p = WgradPlan{WgradEngine::Transposing, tips, tsplits, TG::SLAB, covers && wants_dbig, true, 0, 0};
+    if (kFloat && t_bconv_enabled) p = WgradPlan{WgradEngine::Transposing, tips, tsplits, TG::SLAB, covers && wants_dbig, true, 0, 0, p.high};
   }
   p.chan_off = round256(slabs);
   p.need = p.chan_off + (size_t)chansum_splits(nimg, G::CB, G::PB) * G::CB * sizeof(float);
@@ -788,10 +820,12 @@ static int conv_wgrad_t(int64_t nimg, const float* small, const BigT* big, float
   int rc = REPO_E_BADARG;
   switch (p.engine) {
     case WgradEngine::Transposing:
-      if constexpr (R::TwNBK > 0 && kFloat) rc = launch_tconv_wgrad<G, R::TwNBK, R::TwNPW>(a, p.splits, s);
+      if constexpr (R::TwNBK > 0 && kFloat)
+        rc = p.high ? launch_tconv_wgrad<G, R::TwNBK, R::TwNPW, 3>(a, p.splits, s) : launch_tconv_wgrad<G, R::TwNBK, R::TwNPW, 6>(a, p.splits, s);
       break;
     case WgradEngine::Bf16:
-      if constexpr (kOn<typename R::WgradBf> && kFloat) rc = launch_bconv_wgrad<G, typename R::WgradBf>(a, p.splits, s);
+      if constexpr (kOn<typename R::WgradBf> && kFloat)
+        rc = p.high ? launch_bconv_wgrad<G, typename R::WgradBf, 3>(a, p.splits, s) : launch_bconv_wgrad<G, typename R::WgradBf, 6>(a, p.splits, s);
       break;
     case WgradEngine::Fp32: rc = launch_dconv_wgrad<G, BigT, typename R::Wgrad>(a, p.splits, s); break;
   }
@@ -843,6 +877,7 @@ extern "C" int repo_conv_down(int layer, int64_t nimg, const void* big, int big_
                               int accumulate_dbias, unsigned char* relu_cmask, void* ws, size_t ws_bytes,
                               hipStream_t stream) {
   REPO_ARCH_GUARD();
+  REPO_CONV_PRECISION_GUARD();
   REPO_REQUIRE(nimg >= 0, REPO_E_SHAPE);
   if (nimg == 0) return REPO_OK;
   REPO_REQUIRE(big && w && small, REPO_E_BADARG);
@@ -874,12 +909,21 @@ extern "C" int repo_debug_bconv(int enable) {
   return prev;
 }
 
+extern "C" int repo_conv_precision(int mode) {
+  if (mode != REPO_CONV_PRECISION_HIGHEST && mode != REPO_CONV_PRECISION_HIGH) return REPO_E_BADARG;
+  const int prev = conv_precision();
+  if (prev < 0) return prev;   // REPO_CONV_PRECISION names no mode: nothing is set over it
+  t_conv_precision = mode;
+  return prev;
+}
+
 extern "C" size_t repo_conv_up_workspace_bytes(int layer) {
   REPO_LAYER_SWITCH(layer, return (up_plan<G>(0, REPO_EPI_NONE, 0).total))
 }
 
 extern "C" int repo_conv_up_pack(int layer, const float* w, void* ws, size_t ws_bytes, hipStream_t stream) {
   REPO_ARCH_GUARD();
+  REPO_CONV_PRECISION_GUARD();
   REPO_REQUIRE(w, REPO_E_BADARG);
   REPO_LAYER_SWITCH(layer, return (conv_up_pack_t<G>(w, ws, ws_bytes, stream)))
 }
@@ -888,6 +932,7 @@ extern "C" int repo_conv_up(int layer, int64_t nimg, const float* small, const f
                             float* big, int epi, const float* aux, int ws_is_packed, void* ws, size_t ws_bytes,
                             hipStream_t stream) {
   REPO_ARCH_GUARD();
+  REPO_CONV_PRECISION_GUARD();
   REPO_REQUIRE(nimg >= 0, REPO_E_SHAPE);
   if (nimg == 0) return REPO_OK;
   REPO_REQUIRE(small && w && big, REPO_E_BADARG);
@@ -905,6 +950,7 @@ extern "C" int repo_conv_wgrad(int layer, int64_t nimg, const float* small, cons
                                float* dw, float* dbias_small, float* dbias_big, int accumulate, void* ws,
                                size_t ws_bytes, hipStream_t stream) {
   REPO_ARCH_GUARD();
+  REPO_CONV_PRECISION_GUARD();
   REPO_REQUIRE(nimg > 0, REPO_E_SHAPE);
   REPO_REQUIRE(small && big && dw, REPO_E_BADARG);
   if (big_is_u8) {
@@ -940,9 +986,11 @@ static int decoder_out_nll_t(int64_t nimg, const float* h3, const float* w, cons
             (unsigned)(nimg * G::CS * G::PS * sizeof(float))};
   // ONE decision: the bf16x6 kernel (bdec4.h), whose per-channel partials are the bias gradient's, or -- repo_debug_bconv(0)
   // -- the fp32-MFMA twin with a channel-sum pass over dpre
+  // ... and, on the bf16 kernel, its six- or three-product instantiation (repo_conv_precision)
   const bool bf = t_bconv_enabled != 0;
   a.chan_partials = bf && dbias ? chan : nullptr;
-  if (bf) hipLaunchKernelGGL((bdec4_nll_kernel<TgtT>), dim3(nparts), dim3(256), 0, stream, a);
+  if (bf && conv_precision_high()) hipLaunchKernelGGL((bdec4_nll_kernel<TgtT, 3>), dim3(nparts), dim3(256), 0, stream, a);
+  else if (bf) hipLaunchKernelGGL((bdec4_nll_kernel<TgtT, 6>), dim3(nparts), dim3(256), 0, stream, a);
   else hipLaunchKernelGGL((dconv_dec4_nll_kernel<TgtT>), dim3(nparts), dim3(256), 0, stream, a);
   REPO_CHECK_LAUNCH();
   if (loss_sum) {
@@ -963,6 +1011,7 @@ extern "C" int repo_decoder_out_nll(int64_t nimg, const float* h3, const float* 
                                     unsigned char* relu_mask4, float* loss_sum, float* dbias, int accumulate_dbias,
                                     void* ws, size_t ws_bytes, hipStream_t stream) {
   REPO_ARCH_GUARD();
+  REPO_CONV_PRECISION_GUARD();
   REPO_REQUIRE(nimg > 0, REPO_E_SHAPE);
   REPO_REQUIRE(h3 && w && target, REPO_E_BADARG);
   REPO_REQUIRE(nimg * (int64_t)GDec4::CS * GDec4::PS < kMaxBufElems, REPO_E_SHAPE);

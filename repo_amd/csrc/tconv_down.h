@@ -91,8 +91,12 @@ __global__ __launch_bounds__(256) void tconv_down_pack_kernel(const float* w, ch
 
 // KEPI: REPO_EPI_NONE, REPO_EPI_MUL_DRELU (aux = the fp32 activation whose ReLU the gradient passes through) or
 // REPO_EPI_RELU (+ bias; + the output's channel-quad mask when p.cmask: a lane's four accumulator rows ARE one channel quad)
-template <class T, int KEPI>
+// NPROD (bgemm.h, BgProd): 6 products per (step, tile) and row tile, or the list's last 3 ("high") -- then the third plane of
+// the patch is neither split nor stored and no third-plane fragment is read (the weight groups are still copied whole: their
+// planes interleave per step)
+template <class T, int KEPI, int NPROD>
 __global__ __launch_bounds__(512) void tconv_down_kernel(DownArgs p) {
+  constexpr int NPLN = BgProd<NPROD>::PLANES;
   extern __shared__ __attribute__((aligned(16))) char td_lds[];
   char* const Pb = td_lds;
   char* const Wr = td_lds + 2 * T::PBUF;
@@ -196,12 +200,12 @@ __global__ __launch_bounds__(512) void tconv_down_kernel(DownArgs p) {
 #pragma unroll
           for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int q = 0; q < 3; ++q)
+            for (int q = 0; q < NPLN; ++q)
               fa[m][q] = *reinterpret_cast<const bg_bf16x8*>(Wl + k * T::WSTEP + q * T::WPL + abase + m * 1024);
         };
         auto load_b = [&](bg_bf16x8(&fb)[3], int s, int t) __attribute__((always_inline)) {
 #pragma unroll
-          for (int q = 0; q < 3; ++q) fb[q] = *reinterpret_cast<const bg_bf16x8*>(Pl + q * T::PPLANE + nbase[t] + toff[s]);
+          for (int q = 0; q < NPLN; ++q) fb[q] = *reinterpret_cast<const bg_bf16x8*>(Pl + q * T::PPLANE + nbase[t] + toff[s]);
         };
         // (the patch does not change inside a chunk: the first two items' B fragments of groups 1, 2 were requested in
         // front of the barrier that ended the group before)
@@ -220,7 +224,7 @@ __global__ __launch_bounds__(512) void tconv_down_kernel(DownArgs p) {
           // per accumulator the smallest terms first; the two row tiles interleaved
           constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
 #pragma unroll
-          for (int pr = 0; pr < 6; ++pr)
+          for (int pr = BgProd<NPROD>::FIRST; pr < 6; ++pr)
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #ifdef TCD_NO_MFMA
@@ -325,7 +329,7 @@ __global__ __launch_bounds__(512) void tconv_down_kernel(DownArgs p) {
           char* dst = base + (e & 1) * T::PO + (e >> 1) * T::PIXB;
           *reinterpret_cast<bg_u32x2*>(dst) = bg_u32x2{a1, b1};
           *reinterpret_cast<bg_u32x2*>(dst + T::PPLANE) = bg_u32x2{a2, b2};
-          *reinterpret_cast<bg_u32x2*>(dst + 2 * T::PPLANE) = bg_u32x2{a3, b3};
+          if constexpr (NPLN > 2) *reinterpret_cast<bg_u32x2*>(dst + 2 * T::PPLANE) = bg_u32x2{a3, b3};
         }
       }
     };
@@ -368,19 +372,19 @@ __global__ __launch_bounds__(512) void tconv_down_kernel(DownArgs p) {
   }
 }
 
-template <class T, int KEPI>
+template <class T, int KEPI, int NPROD>
 inline int launch_tconv_down_k(const DownArgs& a, int grid, hipStream_t s) {
   static_assert(T::LDS_BYTES <= 160 * 1024, "tconv_down: LDS");
-  hipError_t e = hipFuncSetAttribute((const void*)tconv_down_kernel<T, KEPI>, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES);
+  hipError_t e = hipFuncSetAttribute((const void*)tconv_down_kernel<T, KEPI, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((tconv_down_kernel<T, KEPI>), dim3((unsigned)grid), dim3(512), T::LDS_BYTES, s, a);
+  hipLaunchKernelGGL((tconv_down_kernel<T, KEPI, NPROD>), dim3((unsigned)grid), dim3(512), T::LDS_BYTES, s, a);
   e = hipGetLastError();
   return e == hipSuccess ? REPO_OK : (int)e;
 }
 
 // pack (>= T::PACK_BYTES) is written here: the weights change once per optimiser step, the pack is one small launch per call.
 // T = TcdGeo: a.epi NONE / MUL_DRELU, no bias;  T = TcdGeoE2: a.epi RELU (+ a.bias, + a.cmask)
-template <class T>
+template <class T, int NPROD>
 inline int launch_tconv_down(const DownArgs& a, const float* w, char* pack, hipStream_t s) {
   hipLaunchKernelGGL(tconv_down_pack_kernel<T>, dim3((T::NCH * T::NST * T::CS * 4 + 255) / 256), dim3(256), 0, s, w, pack);
   hipError_t e = hipGetLastError();
@@ -394,8 +398,8 @@ inline int launch_tconv_down(const DownArgs& a, const float* w, char* pack, hipS
       cus = 256;
   }
   const int grid = a.nimg < cus ? a.nimg : cus;
-  if (a.epi == REPO_EPI_RELU) return launch_tconv_down_k<T, REPO_EPI_RELU>(b, grid, s);
-  return a.epi == REPO_EPI_MUL_DRELU ? launch_tconv_down_k<T, REPO_EPI_MUL_DRELU>(b, grid, s) : launch_tconv_down_k<T, REPO_EPI_NONE>(b, grid, s);
+  if (a.epi == REPO_EPI_RELU) return launch_tconv_down_k<T, REPO_EPI_RELU, NPROD>(b, grid, s);
+  return a.epi == REPO_EPI_MUL_DRELU ? launch_tconv_down_k<T, REPO_EPI_MUL_DRELU, NPROD>(b, grid, s) : launch_tconv_down_k<T, REPO_EPI_NONE, NPROD>(b, grid, s);
 }
 
 }  // namespace repo

@@ -59,8 +59,11 @@ __global__ __launch_bounds__(256) void tconv_up_pack_kernel(const float* __restr
   for (int q = 0; q < 3; ++q) *reinterpret_cast<u32x4s*>(dst + q * 1024) = u32x4s{pl[q][0], pl[q][1], pl[q][2], pl[q][3]};
 }
 
-template <int KEPI>   // REPO_EPI_NONE, REPO_EPI_MUL_DRELU (the encoder backward's) or REPO_EPI_MUL_CMASK: one epilogue per instance keeps the allocation clean
+// NPROD (bgemm.h, BgProd): 6 products per (tap, row) and column parity, or the list's last 3 ("high") -- then the third plane of
+// the staged input is neither split nor stored and no third-plane fragment is loaded
+template <int KEPI, int NPROD>   // REPO_EPI_NONE, REPO_EPI_MUL_DRELU (the encoder backward's) or REPO_EPI_MUL_CMASK: one epilogue per instance keeps the allocation clean
 __global__ __launch_bounds__(256) void tconv_up_kernel(TcuArgs p) {
+  constexpr int NPLN = BgProd<NPROD>::PLANES;
   extern __shared__ __attribute__((aligned(16))) char tcu_lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(256) void tconv_up_kernel(TcuArgs p) {
           char* dst = buf + (cq >> 1) * kTcuOct + ((sy + 1) * kTcuGrid + sx + 1) * 16 + (cq & 1) * 8;
           *reinterpret_cast<bg_u32x2*>(dst) = bg_u32x2{a1, b1};
           *reinterpret_cast<bg_u32x2*>(dst + kTcuPlane) = bg_u32x2{a2, b2};
-          *reinterpret_cast<bg_u32x2*>(dst + 2 * kTcuPlane) = bg_u32x2{a3, b3};
+          if constexpr (NPLN > 2) *reinterpret_cast<bg_u32x2*>(dst + 2 * kTcuPlane) = bg_u32x2{a3, b3};
           ++sx;
           if (sx == 14) sx = 0, ++sy;
         }
@@ -127,13 +130,13 @@ __global__ __launch_bounds__(256) void tconv_up_kernel(TcuArgs p) {
     for (int c = 0; c < 2; ++c) {
       const unsigned base = (unsigned)((((((2 * py + c) * 4 + t) * 2 + h) * 2 + mt) * 3)) * 1024u + 16u * (unsigned)lane;
 #pragma unroll
-      for (int q = 0; q < 3; ++q) fa[c][q] = __builtin_bit_cast(bg_bf16x8, VecLoad<4>::load(rpk, base + (unsigned)q * 1024u));
+      for (int q = 0; q < NPLN; ++q) fa[c][q] = __builtin_bit_cast(bg_bf16x8, VecLoad<4>::load(rpk, base + (unsigned)q * 1024u));
     }
   };
   const int blane = g * kTcuOct + j * 16;
   auto load_b = [&](bg_bf16x8(&fb)[3], const char* buf, int t, int toff) __attribute__((always_inline)) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q) fb[q] = *reinterpret_cast<const bg_bf16x8*>(buf + q * kTcuPlane + blane + t * (kTcuGrid * 16) + toff);
+    for (int q = 0; q < NPLN; ++q) fb[q] = *reinterpret_cast<const bg_bf16x8*>(buf + q * kTcuPlane + blane + t * (kTcuGrid * 16) + toff);
   };
   // the pair (2 x', 2 x' + 1) of row t, channel 16 mt + 4 g (+ r via the scalar offset): lane 15 takes (29, 30) -- its own
   // second column does not exist and the row's last pixel must not spill into the next row
@@ -200,7 +203,7 @@ __global__ __launch_bounds__(256) void tconv_up_kernel(TcuArgs p) {
         __builtin_amdgcn_sched_barrier(0);
         constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};   // smallest terms first
 #pragma unroll
-        for (int pr = 0; pr < 6; ++pr)
+        for (int pr = BgProd<NPROD>::FIRST; pr < 6; ++pr)
 #pragma unroll
           for (int c = 0; c < 2; ++c)
             acc[t][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[t4][c][PA[pr]], fb[t & 1][PB[pr]], acc[t][c], 0, 0, 0);
@@ -278,6 +281,7 @@ inline int launch_tconv_up_pack(const float* w, char* pack, hipStream_t s) {
   return e == hipSuccess ? REPO_OK : (int)e;
 }
 
+template <int NPROD>
 inline int launch_tconv_up(const float* small, const char* pack, const float* bias, const void* aux, float* out, int64_t nimg,
                            int epi, hipStream_t s) {
   const int ipw = (int)((nimg + 255) / 256);
@@ -285,17 +289,17 @@ inline int launch_tconv_up(const float* small, const char* pack, const float* bi
   TcuArgs a{small, pack, bias, aux, out, (int)nimg, epi, ipw, (unsigned)(nimg * 64 * 196 * sizeof(float))};
   hipError_t e;
   if (epi == REPO_EPI_MUL_CMASK) {
-    e = hipFuncSetAttribute((const void*)tconv_up_kernel<REPO_EPI_MUL_CMASK>, hipFuncAttributeMaxDynamicSharedMemorySize, kTcuLds);
+    e = hipFuncSetAttribute((const void*)tconv_up_kernel<REPO_EPI_MUL_CMASK, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, kTcuLds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(tconv_up_kernel<REPO_EPI_MUL_CMASK>, dim3((unsigned)nwg), dim3(256), kTcuLds, s, a);
+    hipLaunchKernelGGL((tconv_up_kernel<REPO_EPI_MUL_CMASK, NPROD>), dim3((unsigned)nwg), dim3(256), kTcuLds, s, a);
   } else if (epi == REPO_EPI_MUL_DRELU) {
-    e = hipFuncSetAttribute((const void*)tconv_up_kernel<REPO_EPI_MUL_DRELU>, hipFuncAttributeMaxDynamicSharedMemorySize, kTcuLds);
+    e = hipFuncSetAttribute((const void*)tconv_up_kernel<REPO_EPI_MUL_DRELU, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, kTcuLds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(tconv_up_kernel<REPO_EPI_MUL_DRELU>, dim3((unsigned)nwg), dim3(256), kTcuLds, s, a);
+    hipLaunchKernelGGL((tconv_up_kernel<REPO_EPI_MUL_DRELU, NPROD>), dim3((unsigned)nwg), dim3(256), kTcuLds, s, a);
   } else {
-    e = hipFuncSetAttribute((const void*)tconv_up_kernel<REPO_EPI_NONE>, hipFuncAttributeMaxDynamicSharedMemorySize, kTcuLds);
+    e = hipFuncSetAttribute((const void*)tconv_up_kernel<REPO_EPI_NONE, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, kTcuLds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(tconv_up_kernel<REPO_EPI_NONE>, dim3((unsigned)nwg), dim3(256), kTcuLds, s, a);
+    hipLaunchKernelGGL((tconv_up_kernel<REPO_EPI_NONE, NPROD>), dim3((unsigned)nwg), dim3(256), kTcuLds, s, a);
   }
   e = hipGetLastError();
   return e == hipSuccess ? REPO_OK : (int)e;

@@ -92,9 +92,13 @@ struct TWGeo {
   static constexpr int own_from(int j) { return j == 0 ? 0 : cmax(0, sy0(j - 1) + nrows(j - 1) - sy0(j)); }
 };
 
-template <class G, int NBK, int NPW>
+// NPROD (bgemm.h, BgProd): 6 products per (block, tap) and row tile, or the list's last 3 ("high") -- then the third planes of
+// `small` and `big` are neither split nor stored and no third-plane fragment is read; db and the channel sums of `big` come
+// from the fp32 values in the staging registers in either case
+template <class G, int NBK, int NPW, int NPROD>
 __global__ __launch_bounds__(256 + 64 * NPW) void tconv_wgrad_kernel(WgradArgs p) {
   using TG = TWGeo<G, NBK, NPW>;
+  constexpr int NPLN = BgProd<NPROD>::PLANES;
   constexpr int NP = TG::NP;
   constexpr int KC = TG::KC, NCH = TG::NCH, XH = TG::XH, AP = TG::AP, AQ = TG::AQ;
   constexpr int BPLANE = TG::BPLANE, APLANE = TG::APLANE, H2 = TG::H2, TPW = TG::TPW;
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void tconv_wgrad_kernel(WgradArgs p
       auto load_b = [&](bg_bf16x8(&fb)[3], int o0, int o1, int t) __attribute__((always_inline)) {
         const int toff = (t / H2) * TG::ROWB + (t % H2) * TG::PIXB;
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
+        for (int q = 0; q < NPLN; ++q) {
           const tw_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(TW_LDS(Bl + q * BPLANE + o0 + toff));
           const tw_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(TW_LDS(Bl + q * BPLANE + o1 + toff));
           fb[q] = __builtin_bit_cast(bg_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
@@ -157,7 +161,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void tconv_wgrad_kernel(WgradArgs p
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
-          for (int q = 0; q < 3; ++q)
+          for (int q = 0; q < NPLN; ++q)
             fa[m][q] = *reinterpret_cast<const bg_bf16x8*>(Al + q * APLANE + abase + (m * 16 * AP + 32 * b) * 2);
       };
       // one step = one (block, tap): its 24 MFMAs (four row tiles x six products: a B fragment read once meets all 64 cs
@@ -179,7 +183,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void tconv_wgrad_kernel(WgradArgs p
         // per accumulator the smallest terms first; the four row tiles interleaved: no MFMA waits for its predecessor
         constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
 #pragma unroll
-        for (int pr = 0; pr < 6; ++pr)
+        for (int pr = BgProd<NPROD>::FIRST; pr < 6; ++pr)
 #pragma unroll
           for (int m = 0; m < 4; ++m)
 #ifdef TW_NO_MFMA   // ablation builds (tools/build_variant.sh): results wrong, time meaningful
@@ -290,7 +294,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void tconv_wgrad_kernel(WgradArgs p
         char* dst = Al + (a_cs * AP + 4 * a_pos) * 2;
         *reinterpret_cast<bg_u32x2*>(dst) = bg_u32x2{a1, b1};
         *reinterpret_cast<bg_u32x2*>(dst + APLANE) = bg_u32x2{a2, b2};
-        *reinterpret_cast<bg_u32x2*>(dst + 2 * APLANE) = bg_u32x2{a3, b3};
+        if constexpr (NPLN > 2) *reinterpret_cast<bg_u32x2*>(dst + 2 * APLANE) = bg_u32x2{a3, b3};
       }
 #pragma unroll
       for (int i = 0; i < B_PER; ++i) {
@@ -318,7 +322,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void tconv_wgrad_kernel(WgradArgs p
                                        : base + ((cc & 1) * 2 * XH + (cc >> 1)) * TG::PIXB;
             *reinterpret_cast<bg_u32x2*>(dst) = bg_u32x2{a1, b1};
             *reinterpret_cast<bg_u32x2*>(dst + BPLANE) = bg_u32x2{a2, b2};
-            *reinterpret_cast<bg_u32x2*>(dst + 2 * BPLANE) = bg_u32x2{a3, b3};
+            if constexpr (NPLN > 2) *reinterpret_cast<bg_u32x2*>(dst + 2 * BPLANE) = bg_u32x2{a3, b3};
           }
         }
       }
@@ -385,16 +389,16 @@ __global__ __launch_bounds__(256 + 64 * NPW) void tconv_wgrad_kernel(WgradArgs p
   }
 }
 
-template <class G, int NBK, int NPW>
+template <class G, int NBK, int NPW, int NPROD>
 inline int launch_tconv_wgrad(const WgradArgs& a, int splits, hipStream_t s) {
   using TG = TWGeo<G, NBK, NPW>;
   static_assert(TG::LDS_BYTES <= 160 * 1024, "twgrad: LDS");
-  hipError_t e = hipFuncSetAttribute((const void*)tconv_wgrad_kernel<G, NBK, NPW>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  hipError_t e = hipFuncSetAttribute((const void*)tconv_wgrad_kernel<G, NBK, NPW, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      TG::LDS_BYTES);
   if (e != hipSuccess) return (int)e;
   WgradArgs b = a;
   b.nsplits_tw = splits;
-  hipLaunchKernelGGL((tconv_wgrad_kernel<G, NBK, NPW>), dim3(16u * (unsigned)((splits + 7) / 8)), dim3(TG::NT), TG::LDS_BYTES, s, b);
+  hipLaunchKernelGGL((tconv_wgrad_kernel<G, NBK, NPW, NPROD>), dim3(16u * (unsigned)((splits + 7) / 8)), dim3(TG::NT), TG::LDS_BYTES, s, b);
   e = hipGetLastError();
   return e == hipSuccess ? REPO_OK : (int)e;
 }

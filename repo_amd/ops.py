@@ -208,11 +208,50 @@ def _nt_pays(M, N, K, *operands):
 
 
 # ----------------------------------------------------------------------------- test-aid switches (thread-local in the library)
-_DEBUG_SWITCHES = ("repo_debug_scan_spin_limit", "repo_debug_bgemm", "repo_debug_bconv", "repo_debug_rowtile32")
+# ... and the convolution precision, which is no test aid but is thread-local in the same way and follows a forward into its
+# backward thread with them
+_DEBUG_SWITCHES = ("repo_debug_scan_spin_limit", "repo_debug_bgemm", "repo_debug_bconv", "repo_debug_rowtile32",
+                   "repo_conv_precision")
+
+# config.conv_precision / REPO_CONV_PRECISION: index = REPO_CONV_PRECISION_* (include/repo_hip.h).  "highest" (default): every
+# fp32 product of the bf16 conv kernels as six bf16 products; "high": three (a1 b1 + a1 b2 + a2 b1, 16 significand bits per
+# operand, per output |error| <= 3 * 2^-16 * sum |a||b|) for half the MFMAs.  DESIGN.md 4c.
+CONV_PRECISIONS = ("highest", "high")
+
+
+def _conv_precision_id(name):
+    if name not in CONV_PRECISIONS:
+        raise ValueError(f'conv_precision={name!r}: expected "highest" or "high"')
+    return CONV_PRECISIONS.index(name)
+
+
+def set_conv_precision(name):
+    """Set the calling thread's convolution precision ("highest" | "high"); returns the previous name."""
+    prev = lib().repo_conv_precision(_conv_precision_id(name))
+    check(min(prev, 0), "repo_conv_precision")   # REPO_CONV_PRECISION names no mode
+    return CONV_PRECISIONS[prev]
+
+
+def get_conv_precision():
+    """The calling thread's convolution precision: what it set, else the process's REPO_CONV_PRECISION, else "highest"."""
+    name = set_conv_precision("highest")
+    set_conv_precision(name)
+    return name
+
+
+@contextlib.contextmanager
+def conv_precision(name):
+    """The block's convolutions run at precision `name` on this thread (autograd wrappers carry it into their backward)."""
+    prev = set_conv_precision(name)
+    try:
+        yield
+    finally:
+        set_conv_precision(prev)
 
 
 def debug_snapshot():
-    """The calling thread's four repo_debug_* settings (each setter returns the previous value: set, then restore)."""
+    """The calling thread's repo_debug_* settings and its convolution precision (each setter returns the previous value: set,
+    then restore)."""
     out = []
     for name in _DEBUG_SWITCHES:
         fn = getattr(lib(), name)
