@@ -603,6 +603,27 @@ int repo_normal_entropy(int64_t n, const float* std, float gscale, float* dstd, 
 int repo_lambda_return(int64_t Hm, int64_t N, const float* rewards, const float* values, float gamma,
                        float lambda_, float gret, float* returns, float* drewards, float* dvalues,
                        float* ret_sum, void* ws, size_t ws_bytes, hipStream_t stream);
+/* ABI v14, additions -- the continuation predictor (config.pcont; Hafner et al. 2020: the reference has no
+ * counterpart).  Both use the reduction scheme above (zeroed header, one launch up to 64 blocks: 65536 elements / 16384
+ * columns; the follow-up launch above that; no float atomics).
+ * Bernoulli NLL of a logit against the SOFT target y = target_scale * base[i] (BCE-with-logits):
+ *   loss_i = max(l, 0) - l y + log1p(exp(-|l|));  *sum_out = sum loss_i;  dlogit_i = (sigmoid(l) - y) * scale (nullable).
+ * Finite for every finite logit (|l| = 90 included: exp only ever sees -|l|). */
+int repo_bernoulli_nll(int64_t n, const float* logit, const float* base, float target_scale, float scale,
+                       float* dlogit, float* sum_out, void* ws, size_t ws_bytes, hipStream_t stream);
+/* lambda_return with a PER-ELEMENT discount p = disc_is_logit ? sigmoid(disc) : disc, and the cumulative-product weights
+ * of the actor and value losses.  rewards, values, disc (Hm, N), only rows 0..Hm-2 of rewards and disc are read;
+ *   R_t = r_t + p_t ((1 - lambda) v_{t+1} + lambda R_{t+1}),  R_{Hm-1} = v_{Hm-1};   w_0 = 1, w_t = w_{t-1} p_{t-1}
+ * returns, weights (Hm-1, N); sums2 = {sum w R, sum w}.  drewards, dvalues, ddisc (Hm, N; all three or none): the gradient
+ * of gret * sum_t w_t R_t with w HELD CONSTANT --
+ *   G_t = gret w_t + p_{t-1} lambda G_{t-1} (G_{-1} = 0);  drewards[t] = G_t;  dvalues[t+1] = p_t (1 - lambda) G_t, the
+ *   bootstrap row Hm-1 also receives p_{Hm-2} lambda G_{Hm-2}, dvalues[0] = 0;
+ *   d/dp_t = G_t ((1 - lambda) v_{t+1} + lambda R_{t+1});  ddisc[t] = d/dp_t * p_t (1 - p_t) for logits, d/dp_t otherwise;
+ * row Hm-1 of drewards and ddisc is zero: every element of every output is written.  Hm < 2: REPO_E_SHAPE. */
+int repo_lambda_return_disc(int64_t Hm, int64_t N, const float* rewards, const float* values, const float* disc,
+                            int disc_is_logit, float lambda_, float gret, float* returns, float* weights,
+                            float* drewards, float* dvalues, float* ddisc, float* sums2, void* ws, size_t ws_bytes,
+                            hipStream_t stream);
 
 /* ------------------------------------------------------------------ inverse-dynamics auxiliary (ABI v10)
  * config.inv_dynamics: InverseDynamicsModel (models/utils.py:84-109) trained on DETACHED latents after every

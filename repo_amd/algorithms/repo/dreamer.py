@@ -30,7 +30,7 @@ from ... import ops
 from ...common.buffers import SequenceReplayBuffer
 from ...common.utils import get_device, postprocess, to_np
 from .models.actor_critic import ActorModel, ValueModel
-from .models.decoder import ObservationModel, RewardModel
+from .models.decoder import ContinuationModel, ObservationModel, RewardModel
 from .models.encoder import Encoder
 from .models.rssm import TransitionModel
 from .models.utils import FlatAdam, InverseDynamicsModel
@@ -128,6 +128,7 @@ class Dreamer:
         self._ev_ac_done = None      # AC(k) finished reading the world-model parameters
         self._log_pending = None     # (event, pinned host buffer, meta) of the last enqueued update
         self._pending_extra = None   # (loss sums, gradient norms) a sibling algorithm adds to the update's log
+        self._pending_pcont = None   # config.pcont: the continuation head's BCE sum of the last model step
         self._log_host = torch.empty(32, dtype=torch.float32).pin_memory()
         self._act_graphs = {}
         self._act_graph_enabled = os.environ.get("REPO_ACT_GRAPH", "1") == "1"
@@ -153,6 +154,9 @@ class Dreamer:
     # config.conv_precision = "high" (three-product bf16 convolutions): Dreamer and RePo, both frame sizes; with
     # pixel_obs=False there is no conv and the key is ignored.  The other families refuse any value but "highest".
     _BUILDS_CONV_PRECISION = True
+    # config.pcont = True (a learned continuation predictor in place of the constant discount): Dreamer and RePo.
+    # The sibling families keep the constant gamma: they refuse.
+    _BUILDS_PCONT = True
 
     def build_models(self, config, env):
         self._conv_precision = getattr(config, "conv_precision", "highest")
@@ -175,6 +179,12 @@ class Dreamer:
             raise NotImplementedError(
                 f"inv_dynamics=True: {type(self).__name__} never trains the inverse-dynamics model (neither does the "
                 "reference's); the auxiliary is built for Dreamer, RePo and FinetunedRePo")
+        self._pcont = bool(getattr(config, "pcont", False))
+        self._pcont_scale = float(getattr(config, "pcont_scale", 10.0))
+        if self._pcont and not self._BUILDS_PCONT:
+            raise NotImplementedError(
+                f"pcont=True: {type(self).__name__} discounts its imagined steps by the constant gamma; the continuation "
+                "predictor is built for Dreamer and RePo")
         obs_size = env.observation_space.shape
         action_size = int(np.prod(env.action_space.shape))
         self.action_size = action_size
@@ -182,6 +192,12 @@ class Dreamer:
         if self._symbolic:   # a flat state vector (dreamer.py:53-54): its length is the modules' size and the NLL's constant
             obs_size = self._npix = int(env.observation_space.shape[0])
         self._build_modules(config, env, obs_size, action_size)
+        if self._pcont:
+            # behind the six modules (their default init under a seed does not depend on the switch), ahead of the optimisers:
+            # its parameters are the model optimiser's
+            self.pcont_model = ContinuationModel(
+                config.belief_size, config.state_size, config.hidden_size, config.dense_activation_function
+            ).to(self.device)
         self._build_optimizers(config)
         if self._inv_dyn:
             # behind the value model, as the reference constructs it (dreamer.py:130-141) => same default init under a seed
@@ -223,6 +239,8 @@ class Dreamer:
             + list(self.obs_model.parameters())
             + list(self.reward_model.parameters())
         )
+        if self._pcont:   # behind the reward head: the same bucket of a data-parallel job, the same clip norm
+            self.model_params += list(self.pcont_model.parameters())
         self.model_optimizer = FlatAdam(self.model_params, lr=config.model_lr)
         # the actor's and the critic's flat gradients are the two halves of ONE buffer: a data-parallel job
         # exchanges them as a single 1.18 MB bucket
@@ -251,7 +269,7 @@ class Dreamer:
 
     def toggle_train(self, train=True):
         for m in (self.encoder, self.transition_model, self.obs_model, self.reward_model, self.actor_model,
-                  self.value_model):
+                  self.value_model) + ((self.pcont_model,) if self._pcont else ()):
             m.train(train)
 
     # ------------------------------------------------------------------ helpers
@@ -358,7 +376,25 @@ class Dreamer:
         st["rew_sums"], st["drew"] = ops.scalar_nll(
             r_pred.view(-1), rewards[:-1].reshape(-1).contiguous(), nonterms[:-1].reshape(-1).contiguous(), 1.0 / grow
         )
+        if self._pcont:
+            st["pc_hid"], st["dpc"] = self._pcont_forward(feat, nonterms, grow)
         return st
+
+    def _pcont_forward(self, feat, nonterms, grow):
+        """The continuation head's half of the model loss: logits on the T*B feature rows, BCE against the
+        soft target gamma * nonterm, pcont_scale * mean over ALL rows (no mask).  -> (hidden activations, dlogit); the sum
+        waits in self._pending_pcont for the update's log."""
+        pc, _ = self._pg(self.pcont_model)
+        logit, hid = ops.mlp_fwd(pc, feat, act=self.pcont_model.act)
+        self._pending_pcont, dlogit = ops.bernoulli_nll(logit.view(-1), nonterms[:-1].reshape(-1).contiguous(), self.c.gamma,
+                                                        self._pcont_scale / grow)
+        return hid, dlogit
+
+    def _pcont_backward(self, feat, hid, dlogit, dfeat):
+        """Weight gradients into the head's slice of the flat model gradient, the input gradient ADDED to the reward head's
+        in `dfeat` (attached latents, like the reward head)."""
+        pc, gc = self._pg(self.pcont_model)
+        ops.mlp_bwd(pc, feat, hid, dlogit.view(-1, 1), dparams=gc, dx=dfeat, accumulate_dx=True, act=self.pcont_model.act)
 
     def _world_model_backward(self, st, kl_grads, decoder_attached):
         """reward head -> (decoder) -> reverse scan -> encoder; gradients into the flat model buffer."""
@@ -370,6 +406,8 @@ class Dreamer:
         dfeat = torch.empty(rows, feat.shape[1], device=dev)
         pw, gw = self._pg(self.reward_model)
         ops.mlp_bwd(pw, feat, st["rew_hid"], st["drew"].view(rows, 1), dparams=gw, dx=dfeat, act=self.reward_model.act)
+        if self._pcont:
+            self._pcont_backward(feat, st["pc_hid"], st["dpc"], dfeat)
         pd, gd = self._pg(self.obs_model)
         pr, gr = self._pg(self.transition_model)
         pe, ge = self._pg(self.encoder)
@@ -577,6 +615,10 @@ class Dreamer:
         nr_ = (Hm - 1) * N
         r_pred = torch.empty(Hm * N, 1, device=dev)
         _, r_hid = ops.mlp_fwd(pw, feats[:nr_], out=r_pred[:nr_], act=act_w)
+        if self._pcont:   # the continuation logits of the same rows (frozen head): p[t] = sigmoid, formed in the returns' kernel
+            pc, _ = self._pg(self.pcont_model)
+            c_logit = torch.empty(Hm * N, 1, device=dev)
+            _, c_hid = ops.mlp_fwd(pc, feats[:nr_], out=c_logit[:nr_], act=self.pcont_model.act)
         v_pred, v_hid = ops.mlp_fwd(pv, feats, act=act_v)
         # -- action entropy on the (attached) imagined states (dreamer.py:320-324).  The reference
         #    re-runs the actor on imag[0..Hm-1]; rows of steps 1..Hm-1 are the very inputs the rollout
@@ -596,8 +638,16 @@ class Dreamer:
                                             want_grad=c.latent_ent_coef != 0)
         # -- lambda returns and the actor objective
         gret = -1.0 / ((Hm - 1) * gN)
-        returns, dr, dv, ret_sum = ops.lambda_return(r_pred.view(Hm, N), v_pred.view(Hm, N), c.gamma, c.gae_lambda,
-                                                     gret)
+        weights = None
+        if self._pcont:
+            # p replaces gamma in the returns, its cumulative product (held constant) weights the actor and value losses:
+            # ret_sum = sum w R, and the value loss below takes the weights as its mask (its sums2[1] = sum w)
+            returns, weights, dr, dv, dc, wr_sums = ops.lambda_return_disc(
+                r_pred.view(Hm, N), v_pred.view(Hm, N), c_logit.view(Hm, N), c.gae_lambda, gret, disc_is_logit=True)
+            ret_sum, weights = wr_sums[:1], weights.view(-1)
+        else:
+            returns, dr, dv, ret_sum = ops.lambda_return(r_pred.view(Hm, N), v_pred.view(Hm, N), c.gamma, c.gae_lambda,
+                                                         gret)
         # -- backward: heads -> entropy path (input gradient only) -> reverse rollout
         #    The value head is differentiated for TWO losses on the same rows and activations: the actor's objective
         #    through the lambda-returns into the imagined states (dreamer.py:343-359, weights frozen) and the critic's
@@ -611,18 +661,21 @@ class Dreamer:
         side = self._ac_side_stream or main
         one_chain = os.environ.get("REPO_VALUE_ONE_CHAIN", "1") == "1"
         if one_chain:
-            v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), None, 1.0 / ((Hm - 1) * gN))
+            v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), weights, 1.0 / ((Hm - 1) * gN))
             ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=gv, dx=dfeat, dout_w=dv2.view(nv, 1), act=act_v)
         else:
             ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
         ops.mlp_bwd(pw, feats[:nr_], r_hid, dr.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_], accumulate_dx=True,
                     act=act_w)
+        if self._pcont:   # through p inside the returns into the imagined states; the head's weights take nothing
+            ops.mlp_bwd(pc, feats[:nr_], c_hid, dc.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_], accumulate_dx=True,
+                        act=self.pcont_model.act)
         # -- the critic's step (one chain: only the optimiser step is left of it), forked onto a side stream: it runs
         #    while the reverse rollout (which fills only ~77 CUs) and the actor backward proceed on the main stream
         side.wait_stream(main)  # after the value head's backward above read the weights
         with torch.cuda.stream(side):
             if not one_chain:
-                v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), None, 1.0 / ((Hm - 1) * gN))
+                v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), weights, 1.0 / ((Hm - 1) * gN))
                 ops.mlp_bwd(pv, feats[:nv], [h[:nv] for h in v_hid], dv2.view(nv, 1), dparams=gv, dx=None, act=act_v)
             if self.dp is None:
                 self.value_optimizer.clip_and_step(c.grad_clip_norm)
@@ -673,6 +726,10 @@ class Dreamer:
             xs.record_stream(cur)
             xn.record_stream(cur)
         self._pending_extra = None
+        if self._pcont:   # the continuation head's BCE sum: the last of the extra per-rank partial sums
+            pcs, self._pending_pcont = self._pending_pcont, None
+            pcs.record_stream(cur)
+            xs = torch.cat([xs, pcs])
         parts = [msc[:4], ret_sum, ent_sum, lat_sum, v_sums, xs, msc[4:5], self.actor_optimizer.sqnorm,
                  self.value_optimizer.sqnorm, xn]
         if dual is not None:
@@ -731,12 +788,19 @@ class Dreamer:
         else:
             out["train/kl_loss"] = kl / grow
         out["train/model_loss"] = out["train/obs_loss"] + out["train/reward_loss"] + out["train/kl_loss"]
+        if self._pcont:   # [.., BCE sum] (see _log_update)
+            xsums, pc_sum = xsums[:-1], xsums[-1]
+            out["train/pcont_loss"] = self._pcont_scale * pc_sum / grow
+            out["train/model_loss"] += out["train/pcont_loss"]
         self._extra_scalars(out, xsums, xnorms, grow)
         action_entropy = ent / (Hm * gN)
         latent_entropy = lat / (Hm * gN) + self._LATENT_ENTROPY_SHIFT * self.c.state_size
         out["train/actor_loss"] = (-ret / ((Hm - 1) * gN) - c.action_ent_coef * action_entropy
                                    - c.latent_ent_coef * latent_entropy)
-        out["train/value_loss"] = vsq / ((Hm - 1) * gN) + 0.5 * LOG_2PI
+        if self._pcont:   # ret = sum w R, _vn = sum w: the weighted means over the (Hm - 1) * gN elements
+            out["train/value_loss"] = (vsq + 0.5 * LOG_2PI * _vn) / ((Hm - 1) * gN)
+        else:
+            out["train/value_loss"] = vsq / ((Hm - 1) * gN) + 0.5 * LOG_2PI
         out["train/action_entropy"] = action_entropy
         out["train/latent_entropy"] = latent_entropy
         self._last_scalars = out
@@ -980,6 +1044,8 @@ class Dreamer:
             "actor_optimizer": self.actor_optimizer.state_dict(),
             "value_optimizer": self.value_optimizer.state_dict(),
         }
+        if self._pcont:
+            params["pcont_model"] = sd(self.pcont_model)
         if self._inv_dyn:   # dreamer.py:517-519
             params["inv_dynamics"] = sd(self.inv_dynamics)
             params["inv_dynamics_optimizer"] = self.inv_dynamics_optimizer.state_dict()
@@ -1015,6 +1081,8 @@ class Dreamer:
         self.model_optimizer.load_state_dict(params["model_optimizer"])
         self.actor_optimizer.load_state_dict(params["actor_optimizer"])
         self.value_optimizer.load_state_dict(params["value_optimizer"])
+        if self._pcont and "pcont_model" in params:   # optional, like the reference's optional modules
+            self._load_module(self.pcont_model, params["pcont_model"])
         if self._inv_dyn and "inv_dynamics" in params:   # a checkpoint without them loads (dreamer.py:560-564)
             self._load_module(self.inv_dynamics, params["inv_dynamics"])
             self.inv_dynamics_optimizer.load_state_dict(params["inv_dynamics_optimizer"])

@@ -124,3 +124,8 @@ class _ScalarHead(nn.Module):
 
 class RewardModel(_ScalarHead):
     pass
+
+
+class ContinuationModel(_ScalarHead):
+    """config.pcont: the continuation predictor of Hafner et al. 2020 (the reference has none).  The reward
+    head's four layers; its output is the LOGIT of the probability that the episode goes on behind this latent."""

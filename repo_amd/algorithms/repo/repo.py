@@ -83,6 +83,8 @@ class RePo(Dreamer):
         r_pred, r_hid = ops.mlp_fwd(pw, feat, act=self.reward_model.act)
         rew_sums, drew = ops.scalar_nll(r_pred.view(-1), rewards[:-1].reshape(-1).contiguous(),
                                         nonterms[:-1].reshape(-1).contiguous(), 1.0 / grow)
+        if self._pcont:
+            pc_hid, dpc = self._pcont_forward(feat, nonterms, grow)
         alpha = c.prior_train_steps / (1 + c.prior_train_steps)
         kl_sum, klg = ops.kl_balance(sv.prior_mean, sv.prior_std, sv.post_mean, sv.post_std, 0, alpha, self.log_beta, 0.0,
                                      1.0 / grow)
@@ -91,8 +93,10 @@ class RePo(Dreamer):
         with torch.cuda.stream(side):
             dfeat = torch.empty(rows, D + S, device=dev)
             ops.mlp_bwd(pw, feat, r_hid, drew.view(rows, 1), dparams=gw, dx=dfeat, act=self.reward_model.act)
+            if self._pcont:
+                self._pcont_backward(feat, pc_hid, dpc, dfeat)
             ev_rew = torch.cuda.Event()
-            ev_rew.record(side)   # the reward head's gradients (part of the decoder bucket) are final
+            ev_rew.record(side)   # the scalar heads' gradients (part of the decoder bucket) are final
             dembeds = torch.empty(rows, c.embedding_size, device=dev)
             ops.rssm_observe_bwd(pr, sv, gr, dfeat=dfeat, dpm=klg[0], dps=klg[1], dqm=klg[2], dqs=klg[3], dembeds=dembeds,
                                  min_std=self.transition_model.min_std_dev)

@@ -57,16 +57,19 @@ class FreezeParameters(contextlib.AbstractContextManager):
 
 
 def lambda_return(rewards, values, discounts, bootstrap, lambda_=0.95):
-    """TD(lambda) returns on the HIP kernel (repo_lambda_return).  The kernel takes ONE discount
-    (dreamer.py:342 builds gamma*ones); a tensor that is not constant raises."""
+    """TD(lambda) returns on the HIP kernels.  A constant `discounts` tensor (dreamer.py:342 builds gamma*ones) takes
+    repo_lambda_return with that ONE discount; any other tensor -- a continuation predictor's probabilities -- takes
+    repo_lambda_return_disc, which reads a discount per element."""
     from .. import ops
 
     gamma = float(discounts.reshape(-1)[0])
-    if not bool((discounts == gamma).all()):
-        raise NotImplementedError("lambda_return kernel supports a constant discount only")
     pad = torch.zeros_like(bootstrap).unsqueeze(0)
-    out = ops.lambda_return(torch.cat([rewards, pad]).contiguous(), torch.cat([values, bootstrap.unsqueeze(0)]).contiguous(),
-                            gamma, lambda_, want_grads=False)
+    r = torch.cat([rewards, pad]).contiguous()
+    v = torch.cat([values, bootstrap.unsqueeze(0)]).contiguous()
+    if not bool((discounts == gamma).all()):
+        d = torch.cat([discounts.expand_as(rewards).float(), pad]).contiguous()
+        return ops.lambda_return_disc(r, v, d, lambda_, disc_is_logit=False, want_grads=False)[0]
+    out = ops.lambda_return(r, v, gamma, lambda_, want_grads=False)
     return out[0]
 
 

@@ -258,6 +258,102 @@ __global__ __launch_bounds__(256) void lambda_return_kernel(int Hm, int N, const
   last_block_finishes(parts, 1, red_out, ticket, red);
 }
 
+// ------------------------------------------------------------------ continuation predictor (config.pcont)
+// Bernoulli NLL of a logit against the soft target y = target_scale * base (BCE-with-logits):
+//   loss = max(l, 0) - l y + log1p(exp(-|l|));  parts[blk] = sum loss;  dlogit = (sigmoid(l) - y) * scale
+// exp only ever sees -|l|: finite for every finite logit.  libm's expf / log1pf: a streaming kernel, the loads bound it.
+__global__ __launch_bounds__(256) void bernoulli_nll_kernel(int n, const float* __restrict__ logit,
+                                                            const float* __restrict__ base, float target_scale,
+                                                            float scale, float* __restrict__ dlogit,
+                                                            float* __restrict__ parts, float* __restrict__ red_out,
+    unsigned* __restrict__ ticket) {
+  __shared__ float red[16];
+  float acc = 0.f;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float l = logit[i], y = target_scale * base[i];
+    const float e = expf(-fabsf(l));
+    acc += fmaxf(l, 0.f) - l * y + log1pf(e);
+    if (dlogit) {
+      const float inv = 1.f / (1.f + e);
+      dlogit[i] = ((l >= 0.f ? inv : e * inv) - y) * scale;
+    }
+  }
+  const float s = block_sum(acc, red);
+  if (threadIdx.x == 0) parts[blockIdx.x] = s;
+  last_block_finishes(parts, 1, red_out, ticket, red);
+}
+
+// lambda-returns with a per-element discount p (a probability, or a logit: p = sigmoid) and the cumulative-product weights
+// w_0 = 1, w_t = w_{t-1} p_{t-1}.  One thread per column like lambda_return_kernel: the returns backwards over the Hm-1
+// steps, then ONE forward walk for the weights, both sums and the gradient of gret * sum_t w_t R_t with w held constant
+// (the thread reads back the returns it wrote).  parts[0][blk] = sum w R, parts[1][blk] = sum w.
+template <bool LOGIT>
+__global__ __launch_bounds__(256) void lambda_return_disc_kernel(int Hm, int N, const float* __restrict__ r,
+                                                                 const float* __restrict__ v,
+                                                                 const float* __restrict__ disc, float lam, float gret,
+                                                                 float* returns, float* __restrict__ weights,
+                                                                 float* __restrict__ dr, float* __restrict__ dv,
+                                                                 float* __restrict__ dd, float* __restrict__ parts,
+                                                                 float* __restrict__ red_out,
+    unsigned* __restrict__ ticket) {
+  __shared__ float red[16];
+  float awr = 0.f, aw = 0.f;
+  const int L = Hm - 1;
+  auto prob = [&](int t, int n) -> float {
+    const float d = disc[(size_t)t * N + n];
+    if constexpr (LOGIT) {
+      const float e = expf(-fabsf(d)), inv = 1.f / (1.f + e);
+      return d >= 0.f ? inv : e * inv;
+    } else {
+      return d;
+    }
+  };
+  for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
+    const float boot = v[(size_t)L * N + n];
+    float last = boot;
+    for (int t = L - 1; t >= 0; --t) {
+      const float p = prob(t, n);
+      const float nextv = (t == L - 1) ? boot : v[(size_t)(t + 1) * N + n];
+      last = r[(size_t)t * N + n] + p * ((1.f - lam) * nextv + lam * last);
+      returns[(size_t)t * N + n] = last;
+    }
+    const bool grads = dr != nullptr;
+    float w = 1.f, G = 0.f, pprev = 0.f;
+    float Rt = returns[n];
+    if (grads) dv[n] = 0.f;  // values[0] is never read
+    for (int t = 0; t < L; ++t) {
+      const float p = prob(t, n);
+      const float Rnext = (t == L - 1) ? boot : returns[(size_t)(t + 1) * N + n];
+      weights[(size_t)t * N + n] = w;
+      awr += w * Rt;
+      aw += w;
+      if (grads) {
+        G = gret * w + pprev * lam * G;  // total gradient reaching R_t
+        dr[(size_t)t * N + n] = G;
+        const float nextv = (t == L - 1) ? boot : v[(size_t)(t + 1) * N + n];
+        const float dp = G * ((1.f - lam) * nextv + lam * Rnext);
+        dd[(size_t)t * N + n] = LOGIT ? dp * p * (1.f - p) : dp;
+        const float gnext = p * (1.f - lam) * G;
+        if (t < L - 1) dv[(size_t)(t + 1) * N + n] = gnext;
+        else dv[(size_t)L * N + n] = gnext + p * lam * G;  // bootstrap: next_value and the scan seed
+      }
+      w *= p;
+      pprev = p;
+      Rt = Rnext;
+    }
+    if (grads) {
+      dr[(size_t)L * N + n] = 0.f;
+      dd[(size_t)L * N + n] = 0.f;
+    }
+  }
+  const float s0 = block_sum(awr, red);
+  const float s1 = block_sum(aw, red);
+  if (threadIdx.x == 0) {
+    parts[blockIdx.x] = s0;
+    parts[gridDim.x + blockIdx.x] = s1;
+  }
+  last_block_finishes(parts, 2, red_out, ticket, red);
+}
 
 // ------------------------------------------------------------------ SampleDist.mode (models/utils.py:149-158)
 // action[row] = the sample with the highest log-probability among NS draws; eps (NS, rows, A).
@@ -521,6 +617,42 @@ extern "C" int repo_lambda_return(int64_t Hm, int64_t N, const float* rewards, c
                      lambda_, gret, returns, drewards, dvalues, red_parts(ws), ret_sum, red_ticket(ws, blocks));
   REPO_CHECK_LAUNCH();
   return red_finish(ws, blocks, 1, ret_sum, stream);
+}
+
+extern "C" int repo_bernoulli_nll(int64_t n, const float* logit, const float* base, float target_scale, float scale,
+                                  float* dlogit, float* sum_out, void* ws, size_t ws_bytes, hipStream_t stream) {
+  REPO_ARCH_GUARD();
+  REPO_REQUIRE(n > 0 && n < kMaxIdx, REPO_E_SHAPE);
+  REPO_REQUIRE(logit && base && sum_out, REPO_E_BADARG);
+  REPO_REQUIRE(ws && ws_bytes >= repo_reduce_workspace_bytes(), REPO_E_WS_TOO_SMALL);
+  const int blocks = red_blocks(n, 1024);
+  hipLaunchKernelGGL(bernoulli_nll_kernel, dim3(blocks), dim3(256), 0, stream, (int)n, logit, base, target_scale, scale,
+                     dlogit, red_parts(ws), sum_out, red_ticket(ws, blocks));
+  REPO_CHECK_LAUNCH();
+  return red_finish(ws, blocks, 1, sum_out, stream);
+}
+
+extern "C" int repo_lambda_return_disc(int64_t Hm, int64_t N, const float* rewards, const float* values,
+                                       const float* disc, int disc_is_logit, float lambda_, float gret, float* returns,
+                                       float* weights, float* drewards, float* dvalues, float* ddisc, float* sums2,
+                                       void* ws, size_t ws_bytes, hipStream_t stream) {
+  REPO_ARCH_GUARD();
+  REPO_REQUIRE(Hm >= 2 && N > 0 && Hm * N < kMaxIdx, REPO_E_SHAPE);
+  REPO_REQUIRE(rewards && values && disc && returns && weights && sums2 && (disc_is_logit == 0 || disc_is_logit == 1) &&
+                   ((drewards == nullptr) == (dvalues == nullptr)) && ((drewards == nullptr) == (ddisc == nullptr)),
+               REPO_E_BADARG);
+  REPO_REQUIRE(ws && ws_bytes >= repo_reduce_workspace_bytes(), REPO_E_WS_TOO_SMALL);
+  const int blocks = red_blocks(N, 256);
+  if (disc_is_logit)
+    hipLaunchKernelGGL(lambda_return_disc_kernel<true>, dim3(blocks), dim3(256), 0, stream, (int)Hm, (int)N, rewards,
+                       values, disc, lambda_, gret, returns, weights, drewards, dvalues, ddisc, red_parts(ws), sums2,
+                       red_ticket(ws, blocks));
+  else
+    hipLaunchKernelGGL(lambda_return_disc_kernel<false>, dim3(blocks), dim3(256), 0, stream, (int)Hm, (int)N, rewards,
+                       values, disc, lambda_, gret, returns, weights, drewards, dvalues, ddisc, red_parts(ws), sums2,
+                       red_ticket(ws, blocks));
+  REPO_CHECK_LAUNCH();
+  return red_finish(ws, blocks, 2, sums2, stream);
 }
 
 extern "C" int repo_tanh_normal_mode(int64_t rows, int64_t A, int64_t samples, const float* mean, const float* std,

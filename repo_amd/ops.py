@@ -1058,6 +1058,47 @@ def lambda_return(rewards, values, gamma, lambda_, gret=0.0, want_grads=True):
     return returns, dr, dv, out
 
 
+def bernoulli_nll(logit, base, target_scale, scale, want_grad=True, out=None):
+    """BCE-with-logits against the soft target target_scale * base (include/repo_hip.h, repo_bernoulli_nll):
+    -> (sum (1,), dlogit (n,) = (sigmoid(logit) - target) * scale or None)."""
+    n = logit.numel()
+    dev = logit.device
+    assert base.numel() == n
+    dlogit = torch.empty(n, dtype=torch.float32, device=dev) if want_grad else None
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = reduce_ws(dev)
+    check(
+        lib().repo_bernoulli_nll(n, _ptr(_f32c(logit)), _ptr(_f32c(base)), float(target_scale), float(scale),
+                                 _ptr(dlogit), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+        "repo_bernoulli_nll",
+    )
+    return out, dlogit
+
+
+def lambda_return_disc(rewards, values, disc, lambda_, gret=0.0, disc_is_logit=False, want_grads=True):
+    """lambda-returns with a per-element discount and the cumulative-product weights (include/repo_hip.h,
+    repo_lambda_return_disc).  rewards, values, disc (Hm, N); row Hm-1 of rewards and disc is never read.
+    -> (returns (Hm-1, N), weights (Hm-1, N), drewards, dvalues, ddisc (Hm, N) or None, sums2 = [sum w R, sum w])."""
+    Hm, N = rewards.shape
+    dev = rewards.device
+    assert values.shape == (Hm, N) and disc.shape == (Hm, N)
+    returns = torch.empty(max(Hm - 1, 0), N, dtype=torch.float32, device=dev)
+    weights = torch.empty(max(Hm - 1, 0), N, dtype=torch.float32, device=dev)
+    dr, dv, dd = ([torch.empty(Hm, N, dtype=torch.float32, device=dev) for _ in range(3)] if want_grads
+                  else [None] * 3)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = reduce_ws(dev)
+    check(
+        lib().repo_lambda_return_disc(Hm, N, _ptr(_f32c(rewards)), _ptr(_f32c(values)), _ptr(_f32c(disc)),
+                                      int(bool(disc_is_logit)), float(lambda_), float(gret), _ptr(returns),
+                                      _ptr(weights), _ptr(dr), _ptr(dv), _ptr(dd), _ptr(out), _ptr(ws), ws.numel(),
+                                      _stream()),
+        "repo_lambda_return_disc",
+    )
+    return returns, weights, dr, dv, dd, out
+
+
 # ----------------------------------------------------------------------------- optimiser
 def grad_sqnorm(g, out=None):
     if out is None:
