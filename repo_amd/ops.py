@@ -1269,16 +1269,18 @@ def vdb_loss(d, mode, gscale=0.0, tau=None, want_grad=True, out=None):
 
 
 def vdb_head_bwd(z, lat, fc_w, dd, eps=None, noise=(0, 0), beta=None, kl_coef=0.0, extra=None, dfc_w=None, dfc_b=None,
-                 accumulate=False):
-    """-> dz (N, 2Z); dfc_w (Z,) / dfc_b (1,) are written (or accumulated into) when given (repo_vdb_head_bwd)."""
+                 accumulate=False, out=None):
+    """-> dz (N, 2Z); dfc_w (Z,) / dfc_b (1,) are written (or accumulated into) when given (repo_vdb_head_bwd).
+    out: an optional (N, 2Z) view with contiguous rows for dz (e.g. columns of a wider buffer)."""
     N, Z = z.shape[0], z.shape[1] // 2
     dev = z.device
-    dz = torch.empty(N, 2 * Z, dtype=torch.float32, device=dev)
+    dz = torch.empty(N, 2 * Z, dtype=torch.float32, device=dev) if out is None else out
+    assert tuple(dz.shape) == (N, 2 * Z), (dz.shape, N, Z)
     nb = lib().repo_vdb_colsum_workspace_bytes(Z)
     ws = workspace(nb, dev)
     ep, seed, off = _eps_args(eps, noise)
     check(lib().repo_vdb_head_bwd(N, Z, _ptr(z), _ld(z), ep, seed, off, _ptr(_f32c(lat)), _ptr(_f32c(fc_w)), _ptr(_f32c(dd)),
-                                  _ptr(beta), float(kl_coef), _ptr(extra), _ptr(dz), 2 * Z, _ptr(dfc_w), _ptr(dfc_b),
+                                  _ptr(beta), float(kl_coef), _ptr(extra), _ptr(dz), _ld(dz), _ptr(dfc_w), _ptr(dfc_b),
                                   int(accumulate), _ptr(ws), ws.numel(), _stream()), "repo_vdb_head_bwd")
     return dz
 
@@ -1288,13 +1290,16 @@ def vdb_beta_step(beta, kl_real, n_real, kl_fake, n_fake, beta_lr, target_kl, kl
                                    float(target_kl), _ptr(kl_out), _stream()), "repo_vdb_beta_step")
 
 
-def vdb_gp_delta(z, lat, fc_w, eps=None, noise=(0, 0)):
-    """-> delta5 (N, 2Z), the upstream of the gradient penalty's input-gradient chain (repo_vdb_gp_delta)."""
+def vdb_gp_delta(z, lat, fc_w, eps=None, noise=(0, 0), out=None):
+    """-> delta5 (N, 2Z), the upstream of the gradient penalty's input-gradient chain (repo_vdb_gp_delta).
+    out: an optional (N, 2Z) view with contiguous rows for delta5."""
     N, Z = z.shape[0], z.shape[1] // 2
-    out = torch.empty(N, 2 * Z, dtype=torch.float32, device=z.device)
+    if out is None:
+        out = torch.empty(N, 2 * Z, dtype=torch.float32, device=z.device)
+    assert tuple(out.shape) == (N, 2 * Z), (out.shape, N, Z)
     ep, seed, off = _eps_args(eps, noise)
     check(lib().repo_vdb_gp_delta(N, Z, _ptr(z), _ld(z), ep, seed, off, _ptr(_f32c(lat)), _ptr(_f32c(fc_w)), _ptr(out),
-                                  2 * Z, _stream()), "repo_vdb_gp_delta")
+                                  _ld(out), _stream()), "repo_vdb_gp_delta")
     return out
 
 

@@ -74,6 +74,25 @@ def _masks(rs, N):
 @pytest.mark.parametrize("A", [1, 6, 7])
 @pytest.mark.parametrize("N", [1, 63, 64, 65, 257])
 def test_normal_nll_rows(ops, N, A):
+    _normal_nll_rows_case(ops, N, A, ("ones", "one-row", "p0.3", "zeros"), counted=False)
+
+
+@pytest.mark.parametrize("N,A", [(9362, 7), (9363, 7)], ids=["64-blocks", "64-blocks-capped"])
+def test_normal_nll_rows_at_the_grid_cap(ops, N, A):
+    """The grid is min(64, ceil(N A / 1024)): N A = 65534 is the last size with a block per 1024 elements, 65541 the
+    first that asks for 65 and is capped, so that the element loop's stride no longer covers everything in four passes.
+    The assertions of test_normal_nll_rows, and tests.test_reductions_gpu.reduction()'s on the partials and the ticket."""
+    assert -(-N * A // 1024) == {9362: 64, 9363: 65}[N]
+    _normal_nll_rows_case(ops, N, A, ("p0.3", "ones"), counted=True)
+
+
+def _normal_nll_rows_case(ops, N, A, mask_names, counted):
+    """counted: the first call also goes through reduction() -- 2 x blocks finite partials after a NaN fill, the ticket word
+    0 again, sums = the fixed-order sum of the partials, no follow-up kernel."""
+    from tests.reduce_ref import LAST_BLOCK_MAX_GRID
+    from tests.test_reductions_gpu import reduction
+
+    blocks = min(LAST_BLOCK_MAX_GRID, -(-N * A // 1024))      # csrc/invdyn.hip, repo_normal_nll_rows
     rs = np.random.RandomState(1000 * A + N)
     buf = torch.from_numpy(rs.standard_normal((N, 2 * A + 3)).astype(np.float32))
     buf[:, A:2 * A] *= 3.0
@@ -88,10 +107,16 @@ def test_normal_nll_rows(ops, N, A):
     raw_d = buf.cuda()[:, :2 * A]       # ldraw = 2A + 3
     assert raw_d.stride(0) == 2 * A + 3
     for name, mk in _masks(rs, N).items():
+        if name not in mask_names:
+            continue
         mask = torch.from_numpy(mk)
         r64 = buf[:, :2 * A].double().requires_grad_(True)
         total, count = ir.masked_nll(r64, target.double(), mask)
-        sums, draw = ops.normal_nll_rows(raw_d, target.cuda(), mask.cuda())
+        if counted:
+            (sums, draw), _ = reduction(ops, lambda: ops.normal_nll_rows(raw_d, target.cuda(), mask.cuda()), lambda r: r[0],
+                                        "normal_nll_rows_kernel", blocks, 2, f"normal_nll_rows N={N} A={A} {name} blocks={blocks}")
+        else:
+            sums, draw = ops.normal_nll_rows(raw_d, target.cuda(), mask.cuda())
         sums2, draw2 = ops.normal_nll_rows(raw_d, target.cuda(), mask.cuda())
         assert torch.equal(sums, sums2) and torch.equal(draw, draw2), "two runs differ"
         assert not torch.isnan(sums).any() and not torch.isnan(draw).any()
