@@ -798,6 +798,7 @@ int repo_film_tables(int64_t nimg, int nlayers, const int* channels, const float
  *   conv_kind 1: the stride-2 convolution of repo_conv_down, geo = {CB, CS, HB, KS}, x = its `big` input (uint8 frames if
  *                x_is_u8, normalised like repo_conv_down does), w (CS, CB, KS, KS), bias (CS); planes = small channels;
  *   conv_kind 2: its transpose (repo_conv_up), x = the `small` input, same w, bias (CB); planes = big channels;
+ *                HB = 2 (HS - 1) + KS exactly: an odd HB - KS is REPO_E_SHAPE (conv_kind 1 floors HS = (HB - KS) / 2 + 1);
  *   conv_kind 3: dense (the decoder's 1 x 1 -> 5 x 5 first layer), geo = {K, per_element_bias}: y[n][c*P + p] = bias[c] (or
  *                bias[c*P + p] if per_element_bias) + sum_k x[n][k] w[k][c*P + p];
  *   gated_epoch / epoch (nullable / non-zero): one device word, zero-initialised once, and a number that grows from call

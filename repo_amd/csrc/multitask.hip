@@ -392,6 +392,10 @@ extern "C" int repo_film_bwd_h(int64_t nimg, int64_t C, int64_t P, const float* 
     } else {
       const int64_t CB = geo[0], CS = geo[1], HB = geo[2], KS = geo[3];
       REPO_REQUIRE(CB > 0 && CS > 0 && KS > 0 && HB >= KS && CB < 4096 && CS < 4096 && HB < 4096, REPO_E_SHAPE);
+      // a transposed convolution of an HS-wide input is exactly 2 (HS - 1) + KS wide: an odd HB - KS describes no layer (with
+      // the floored HS its last output row and column meet an empty tap range and would come out as the bias alone: a y
+      // of no layer, computed without complaint); the convolution floors, as repo_conv_down does
+      REPO_REQUIRE(conv_kind == 1 || (HB - KS) % 2 == 0, REPO_E_SHAPE);
       const int64_t HS = (HB - KS) / 2 + 1;
       ex.CB = (int)CB; ex.CS = (int)CS; ex.HB = (int)HB; ex.HS = (int)HS; ex.KS = (int)KS;
       // the plane the FiLM acts on is the layer's OUTPUT: a small channel for the convolution, a big one for its transpose

@@ -1158,10 +1158,11 @@ def film_tables(film, channels):
 FILM_CONV_DOWN, FILM_CONV_UP, FILM_DENSE = 1, 2, 3
 
 
-def film_bwd_h(dh, h, film, gamma_off, beta_off, dfilm, dy=None, exact=None):
+def film_bwd_h(dh, h, film, gamma_off, beta_off, dfilm, dy=None, exact=None, epoch_word=True):
     """film_bwd for a layer that ran with EPI_FILM_RELU: only its output h exists, y is recovered from it -- except on
     planes with |1 + gamma| < 1e-3, which recompute y exactly from the layer itself: exact = (FILM_CONV_DOWN | FILM_CONV_UP,
-    layer id, x, w, bias) or (FILM_DENSE, K, x (n, K), w (K, C * P), bias (C))."""
+    layer id or its geometry (CB, CS, HB, KS), x, w, bias) or (FILM_DENSE, K, x (n, K), w (K, C * P), bias (C)).
+    epoch_word=False passes no "a gated-off plane was met" word: the exact pass then reads every plane's scale."""
     n, C = h.shape[:2]
     P = h.numel() // (n * C)
     if dy is None:
@@ -1171,12 +1172,16 @@ def film_bwd_h(dh, h, film, gamma_off, beta_off, dfilm, dy=None, exact=None):
         kind, which, x, w, bias = exact
         # FILM_DENSE: which = K, or (K, True) when `bias` holds one value per output element (the composed decoder head)
         dense = which if isinstance(which, tuple) else (which, False)
-        geo = (ctypes.c_int64 * 4)(*(CONV_GEO[which] if kind != FILM_DENSE else (int(dense[0]), int(bool(dense[1])), 0, 0)))
+        if kind == FILM_DENSE:
+            geo4 = (int(dense[0]), int(bool(dense[1])), 0, 0)
+        else:   # a layer id, or the geometry itself (CB, CS, HB, KS)
+            geo4 = tuple(int(v) for v in which) if isinstance(which, tuple) else CONV_GEO[which]
+        geo = (ctypes.c_int64 * 4)(*geo4)
         assert x.is_contiguous() and w.is_contiguous() and x.dtype in (torch.float32, torch.uint8)
     # the "a gated-off plane was met" word: word 8 of the stream's zeroed reduction workspace, stamped with a call counter
     global _film_epoch
     _film_epoch = _film_epoch % 0xFFFFFFF0 + 1
-    word = reduce_ws(h.device)[32:36]
+    word = reduce_ws(h.device)[32:36] if epoch_word else None
     check(lib().repo_film_bwd_h(n, C, P, _ptr(dh), _ptr(h), _ptr(film), film.shape[1], gamma_off, beta_off, _ptr(dy),
                                 _ptr(dfilm), kind, geo, _ptr(x), int(x is not None and x.dtype == torch.uint8),
                                 _ptr(_f32c(w)) if w is not None else None, _ptr(bias), _ptr(word), _film_epoch,
@@ -1199,14 +1204,14 @@ def film_bwd(dh, y, film, gamma_off, beta_off, dfilm, dy=None):
     return dy
 
 
-def kl_balance_tasks(pm, ps, qm, qs, alpha, log_beta, tasks, target_kl, scale):
+def kl_balance_tasks(pm, ps, qm, qs, alpha, log_beta, tasks, target_kl, scale, want_grads=True):
     """MultitaskRePo's KL balance with the per-row multiplier exp(tasks_row . log_beta) (repo_mt.py:75-93).
-    Returns (sums (3 + C,), [dpm, dps, dqm, dqs])."""
+    Returns (sums (3 + C,), [dpm, dps, dqm, dqs]); want_grads=False: the sums alone, (sums, None)."""
     S = pm.shape[-1]
     rows = pm.numel() // S
     C = log_beta.numel()
     dev = pm.device
-    g = [torch.empty_like(pm) for _ in range(4)]
+    g = [torch.empty_like(pm) if want_grads else None for _ in range(4)]
     sums = torch.empty(3 + C, dtype=torch.float32, device=dev)
     nb = lib().repo_kl_balance_tasks_workspace_bytes()
     ws = workspace(nb, dev)
@@ -1217,7 +1222,7 @@ def kl_balance_tasks(pm, ps, qm, qs, alpha, log_beta, tasks, target_kl, scale):
                                     _stream()),
         "repo_kl_balance_tasks",
     )
-    return sums, g
+    return sums, g if want_grads else None
 
 
 def dual_step_tasks(log_beta, exp_avg, exp_avg_sq, sums, rows, lr, betas, eps, step, apply=True, out=None, skip=None):
