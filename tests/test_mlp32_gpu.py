@@ -2,8 +2,9 @@
 REPO_MLP32_MIN_ROWS=0 and proven from the device trace (the engine's instantiations carry a fifth template argument, 32).
 
 Per case -- rows in {1, 31, 32, 33, 77, 2081} (one lane of a tile, one row short of / exactly / one past a tile, three
-tiles with a ragged last, 66 tiles: more than one tile per workgroup is reached only past 512 tiles, which the update-sized
-cases of tests/test_rssm_gpu.py cover through the default routing) x the value head (230 -> 200^3 -> 1) and the actor head
+tiles with a ragged last, 66 tiles: more than one tile per workgroup is reached only past 2 x CUs tiles, where
+tests/test_mlp_persistent_gpu.py takes both engines through every transition of their tile loops with the helpers of this
+module) x the value head (230 -> 200^3 -> 1) and the actor head
 (230 -> 200^4 -> 12) x ELU / ReLU -- outputs, saved hiddens, dx and every saved pre-activation gradient are compared
 
   * with a float64 restatement of the chain, at the FTOL / GTOL of tests/test_rssm_gpu.py;
@@ -112,9 +113,9 @@ def case(head, act, rows):
     return c
 
 
-def guarded(rows, cols, ld=None, fill=S):
+def guarded(rows, cols, ld=None, fill=S, device="cuda"):
     """-> (buffer of rows + 1 rows of ld columns, all sentinel; its [rows, cols] view)."""
-    buf = torch.full((rows + 1, ld or cols), fill, dtype=torch.float32, device="cuda")
+    buf = torch.full((rows + 1, ld or cols), fill, dtype=torch.float32, device=device)
     return buf, buf[:rows, :cols]
 
 

@@ -85,7 +85,9 @@ def test_observe_fwd_bwd(ops, T, B, A):
     assert e < GTOL
 
 
-# rows >= 16384 run 32-row tiles (csrc/mlp16.hip); 16400 and 17001 leave a ragged last tile.  rows >= 4096: the weight
+# rows >= 4097 run the 32-row bf16x6 chains (csrc/mlp32.hip), below that the 16-row fp32 ones (csrc/mlp16.hip); 16400 and
+# 17001 rows are 513 and 532 tiles, so on 512 workgroup slots the first workgroups take two tiles each, and both leave a
+# ragged last tile (tests/test_mlp_persistent_gpu.py compares that regime row by row, on either engine).  rows >= 4096: the weight
 # gradients of the 200-wide layers take the direct kernel (csrc/wgrad_direct.h): 4097 and 17001 end on a single row
 # (a half k-step), 4100 / 64 row ranges leaves the last ranges empty
 @pytest.mark.parametrize("mod,L,rows", [("reward_model", 4, 333), ("actor_model", 5, 1000), ("value_model", 4, 64),
