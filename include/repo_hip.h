@@ -864,6 +864,21 @@ int repo_grad_sqnorm(int64_t n, const float* g, float* sqnorm, void* ws, size_t 
 int repo_clip_adam(int64_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
                    const float* sqnorm, float max_norm, float lr, float beta1, float beta2, float eps,
                    int64_t step, const unsigned* skip_if_nonzero, hipStream_t stream);
+/* ABI v14, addition -- the slow value target (config.slow_value_target; Hafner et al. 2021: the reference
+ * has no counterpart).  repo_clip_adam's update and, in the SAME pass, the mix of a second flat buffer towards the
+ * parameter value just written:
+ *   p_new, exp_avg, exp_avg_sq: bit for bit what repo_clip_adam writes from the same inputs (same grid: 256 threads,
+ *   min(2048, ceil(n / 256)) blocks, grid-stride loop; kernel clip_adam_target_kernel);
+ *   d = p_new - t;  t_new = fmaf(fraction, d, t);  fraction == 1.0f stores p_new itself (a bit copy).
+ * target: n floats, the layout of params, overlapping none of the other buffers.  fraction in (0, 1].
+ * skip_if_nonzero non-zero: NOTHING is written, the target included -- parameters and target move together or not at all,
+ * which is why the mix is fused into the step and not a launch of its own.  The caller uses this entry only on the steps
+ * that mix; every other step is repo_clip_adam.
+ * target NULL, fraction outside (0, 1] (NaN included): REPO_E_BADARG; n <= 0 or step < 1: REPO_E_SHAPE. */
+int repo_clip_adam_target(int64_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                          const float* sqnorm, float max_norm, float lr, float beta1, float beta2, float eps,
+                          int64_t step, const unsigned* skip_if_nonzero, float* target, float fraction,
+                          hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -157,6 +157,9 @@ class Dreamer:
     # config.pcont = True (a learned continuation predictor in place of the constant discount): Dreamer and RePo.
     # The sibling families keep the constant gamma: they refuse.
     _BUILDS_PCONT = True
+    # config.slow_value_target = True (the lambda-returns read a slowly mixed copy of the value head): Dreamer
+    # and RePo.  The sibling families bootstrap from the critic they are about to step: they refuse.
+    _BUILDS_SLOW_VALUE = True
 
     def build_models(self, config, env):
         self._conv_precision = getattr(config, "conv_precision", "highest")
@@ -185,6 +188,19 @@ class Dreamer:
             raise NotImplementedError(
                 f"pcont=True: {type(self).__name__} discounts its imagined steps by the constant gamma; the continuation "
                 "predictor is built for Dreamer and RePo")
+        self._slow_value = bool(getattr(config, "slow_value_target", False))
+        self._slow_value_update = getattr(config, "slow_value_update", 100)
+        self._slow_value_fraction = float(getattr(config, "slow_value_fraction", 1.0))
+        if self._slow_value and not self._BUILDS_SLOW_VALUE:
+            raise NotImplementedError(
+                f"slow_value_target=True: {type(self).__name__} builds its lambda-returns from the critic it steps; the slow "
+                "value target is built for Dreamer and RePo")
+        if (isinstance(self._slow_value_update, bool) or self._slow_value_update != int(self._slow_value_update)
+                or self._slow_value_update < 1):
+            raise ValueError(f"slow_value_update={self._slow_value_update!r}: expected an integer >= 1 (value-optimiser steps)")
+        self._slow_value_update = int(self._slow_value_update)
+        if not 0.0 < self._slow_value_fraction <= 1.0:
+            raise ValueError(f"slow_value_fraction={self._slow_value_fraction!r}: expected a float in (0, 1]")
         obs_size = env.observation_space.shape
         action_size = int(np.prod(env.action_space.shape))
         self.action_size = action_size
@@ -199,6 +215,8 @@ class Dreamer:
                 config.belief_size, config.state_size, config.hidden_size, config.dense_activation_function
             ).to(self.device)
         self._build_optimizers(config)
+        if self._slow_value:
+            self._build_slow_value(config)
         if self._inv_dyn:
             # behind the value model, as the reference constructs it (dreamer.py:130-141) => same default init under a seed
             self.inv_dynamics = InverseDynamicsModel(
@@ -257,6 +275,24 @@ class Dreamer:
         # REPO_DP_BUCKETS=1: the whole 20.7 MB model gradient as ONE all-reduce after the backward (the round-2
         # exchange; kept for A/B runs on a multi-GPU node and for the bucketed-equals-single test)
         self._dp_two_buckets = os.environ.get("REPO_DP_BUCKETS", "2") != "1"
+
+    def _build_slow_value(self, config):
+        """config.slow_value_target: a second ValueModel whose parameters are views into ONE flat buffer with
+        value_optimizer.flat's layout (same offsets, same padded length), a bit copy of the online head.  Built under a
+        forked generator: it draws nothing from torch's stream, so everything constructed behind it initialises as it
+        does with the key off.  Never in an optimiser, never takes a gradient; the value optimiser mixes it in the
+        launch of its own step (FlatAdam.track_target)."""
+        opt = self.value_optimizer
+        with torch.random.fork_rng(devices=[]):
+            self.slow_value_model = ValueModel(
+                config.belief_size, config.state_size, config.hidden_size, config.dense_activation_function
+            ).to(self.device)
+        self._slow_value_flat = opt.flat.clone()
+        for q, o in zip(self.slow_value_model.plist(), opt.offsets):
+            q.requires_grad_(False)
+            q.data = self._slow_value_flat[o : o + q.numel()].view(q.shape)
+        assert [tuple(q.shape) for q in self.slow_value_model.plist()] == [tuple(q.shape) for q in opt.params]
+        opt.track_target(self._slow_value_flat, self._slow_value_update, self._slow_value_fraction)
 
     def _wgrad_side(self, batch):
         """The weight-gradient side stream for a batch of `batch` sequences, or None (in line)."""
@@ -619,7 +655,16 @@ class Dreamer:
             pc, _ = self._pg(self.pcont_model)
             c_logit = torch.empty(Hm * N, 1, device=dev)
             _, c_hid = ops.mlp_fwd(pc, feats[:nr_], out=c_logit[:nr_], act=self.pcont_model.act)
-        v_pred, v_hid = ops.mlp_fwd(pv, feats, act=act_v)
+        nv = (Hm - 1) * N
+        if self._slow_value:
+            # the returns' values and bootstrap row come from the slow target on all Hm * N rows; the online head runs on
+            # the rows its own loss reads
+            ps, _ = self._pg(self.slow_value_model)
+            vt_pred, vt_hid = ops.mlp_fwd(ps, feats, act=act_v)
+            v_pred, v_hid = ops.mlp_fwd(pv, feats[:nv], act=act_v)
+        else:
+            v_pred, v_hid = ops.mlp_fwd(pv, feats, act=act_v)
+            vt_pred = v_pred
         # -- action entropy on the (attached) imagined states (dreamer.py:320-324).  The reference
         #    re-runs the actor on imag[0..Hm-1]; rows of steps 1..Hm-1 are the very inputs the rollout
         #    already pushed through the actor (detaching does not change values), so only the final
@@ -643,10 +688,10 @@ class Dreamer:
             # p replaces gamma in the returns, its cumulative product (held constant) weights the actor and value losses:
             # ret_sum = sum w R, and the value loss below takes the weights as its mask (its sums2[1] = sum w)
             returns, weights, dr, dv, dc, wr_sums = ops.lambda_return_disc(
-                r_pred.view(Hm, N), v_pred.view(Hm, N), c_logit.view(Hm, N), c.gae_lambda, gret, disc_is_logit=True)
+                r_pred.view(Hm, N), vt_pred.view(Hm, N), c_logit.view(Hm, N), c.gae_lambda, gret, disc_is_logit=True)
             ret_sum, weights = wr_sums[:1], weights.view(-1)
         else:
-            returns, dr, dv, ret_sum = ops.lambda_return(r_pred.view(Hm, N), v_pred.view(Hm, N), c.gamma, c.gae_lambda,
+            returns, dr, dv, ret_sum = ops.lambda_return(r_pred.view(Hm, N), vt_pred.view(Hm, N), c.gamma, c.gae_lambda,
                                                          gret)
         # -- backward: heads -> entropy path (input gradient only) -> reverse rollout
         #    The value head is differentiated for TWO losses on the same rows and activations: the actor's objective
@@ -655,12 +700,16 @@ class Dreamer:
         #    head's reverse chain is per row a unit chain times the row's scalar, so ONE chain serves both
         #    (ops.mlp_bwd, dout_w): round 5 ran it twice -- the second time on a forked side stream, with its own weight
         #    packs -- REPO_VALUE_ONE_CHAIN=0 restores that form.
+        #    With config.slow_value_target the two losses read two heads: the actor's gradient goes through the TARGET's
+        #    chain into the imagined states, the critic's through the online head into its weights -- two chains by
+        #    construction, and REPO_VALUE_ONE_CHAIN is not read.
         dfeat = torch.empty(Hm * N, Fw, device=dev)
-        nv = (Hm - 1) * N
         main = torch.cuda.current_stream(dev)
         side = self._ac_side_stream or main
-        one_chain = os.environ.get("REPO_VALUE_ONE_CHAIN", "1") == "1"
-        if one_chain:
+        one_chain = not self._slow_value and os.environ.get("REPO_VALUE_ONE_CHAIN", "1") == "1"
+        if self._slow_value:
+            ops.mlp_bwd(ps, feats, vt_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
+        elif one_chain:
             v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), weights, 1.0 / ((Hm - 1) * gN))
             ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=gv, dx=dfeat, dout_w=dv2.view(nv, 1), act=act_v)
         else:
@@ -674,7 +723,7 @@ class Dreamer:
         #    while the reverse rollout (which fills only ~77 CUs) and the actor backward proceed on the main stream
         side.wait_stream(main)  # after the value head's backward above read the weights
         with torch.cuda.stream(side):
-            if not one_chain:
+            if not one_chain:   # (slow target: v_pred and v_hid have the nv rows already)
                 v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), weights, 1.0 / ((Hm - 1) * gN))
                 ops.mlp_bwd(pv, feats[:nv], [h[:nv] for h in v_hid], dv2.view(nv, 1), dparams=gv, dx=None, act=act_v)
             if self.dp is None:
@@ -1046,6 +1095,8 @@ class Dreamer:
         }
         if self._pcont:
             params["pcont_model"] = sd(self.pcont_model)
+        if self._slow_value:   # the value head's key names; its phase is value_optimizer's step count
+            params["slow_value_model"] = sd(self.slow_value_model)
         if self._inv_dyn:   # dreamer.py:517-519
             params["inv_dynamics"] = sd(self.inv_dynamics)
             params["inv_dynamics_optimizer"] = self.inv_dynamics_optimizer.state_dict()
@@ -1083,6 +1134,11 @@ class Dreamer:
         self.value_optimizer.load_state_dict(params["value_optimizer"])
         if self._pcont and "pcont_model" in params:   # optional, like the reference's optional modules
             self._load_module(self.pcont_model, params["pcont_model"])
+        if self._slow_value:
+            if "slow_value_model" in params:
+                self._load_module(self.slow_value_model, params["slow_value_model"])
+            else:   # a checkpoint written with the key off: the hard update at step 0, from the head just loaded
+                self._slow_value_flat.copy_(self.value_optimizer.flat)
         if self._inv_dyn and "inv_dynamics" in params:   # a checkpoint without them loads (dreamer.py:560-564)
             self._load_module(self.inv_dynamics, params["inv_dynamics"])
             self.inv_dynamics_optimizer.load_state_dict(params["inv_dynamics_optimizer"])

@@ -36,6 +36,7 @@ class MultitaskDreamer(Dreamer):
     _BUILDS_SYMBOLIC = False       # pixel_obs=False: the state-vector modules are built for Dreamer and RePo
     _BUILDS_CONV_PRECISION = False   # conv_precision="high": built and tested for Dreamer and RePo
     _BUILDS_PCONT = False            # pcont=True: built and tested for Dreamer and RePo
+    _BUILDS_SLOW_VALUE = False       # slow_value_target=True: built and tested for Dreamer and RePo
 
     def __init__(self, config, env, eval_env, logger):
         super().__init__(config, env, eval_env, logger)

@@ -94,6 +94,7 @@ class FlatAdam:
         self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=dev)
         self.sqnorm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.skip = None   # the current update's status word (ops.take_scan_status): non-zero = the step is skipped
+        self.target = None   # (flat, every, fraction) of a tracked slow copy: track_target
         self.gviews = []
         with torch.no_grad():
             for p, o, n in zip(self.params, self.offsets, sizes):
@@ -119,6 +120,7 @@ class FlatAdam:
         self.exp_avg_sq = torch.zeros_like(self.flat)
         self.sqnorm = torch.zeros(1, dtype=torch.float32, device=self.flat.device)
         self.skip = None
+        self.target = None
         self.gviews = parent.gviews[:n_params]
         return self
 
@@ -126,18 +128,37 @@ class FlatAdam:
     def zero_grad(self, set_to_none=False):
         self.grad.zero_()
 
+    def track_target(self, flat, every, fraction):
+        """A slow copy of the parameters (config.slow_value_target): `flat` has this optimiser's layout.  After
+        the step with the 1-based count k, if k % every == 0, flat += fraction * (self.flat - flat) (fraction == 1: a bit
+        copy), in the step's own launch (ops.clip_adam_target) and under its skip word; every other step is the plain one
+        and leaves `flat` alone.  step_count advances on a skipped step too, so a mixing step that a fault skipped is lost
+        until the next period.  The phase is step_count's: a checkpoint restores it with the optimiser's state."""
+        every, fraction = int(every), float(fraction)
+        assert flat.shape == self.flat.shape and flat.dtype == torch.float32 and flat.is_contiguous(), flat.shape
+        assert flat.device == self.flat.device and flat.data_ptr() != self.flat.data_ptr()
+        assert every >= 1 and 0.0 < fraction <= 1.0, (every, fraction)
+        self.target = (flat, every, fraction)
+
+    def _step(self, sqnorm, max_norm):
+        target = self.target
+        if target is not None and self.step_count % target[1] == 0:
+            ops.clip_adam_target(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, sqnorm, max_norm, self.lr,
+                                 self.step_count, target[0], target[2], self.betas, self.eps, skip=self.skip)
+        else:
+            ops.clip_adam(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, sqnorm, max_norm, self.lr,
+                          self.step_count, self.betas, self.eps, skip=self.skip)
+
     def clip_and_step(self, max_norm):
         """clip_grad_norm_(params, max_norm) + step() (repo.py:89-90).  The squared global
         norm stays on the device in self.sqnorm (read it after the update's single sync)."""
         self.step_count += 1
         ops.grad_sqnorm(self.grad, out=self.sqnorm)
-        ops.clip_adam(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.sqnorm, max_norm, self.lr,
-                      self.step_count, self.betas, self.eps, skip=self.skip)
+        self._step(self.sqnorm, max_norm)
 
     def step(self):
         self.step_count += 1
-        ops.clip_adam(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, None, 0.0, self.lr, self.step_count,
-                      self.betas, self.eps, skip=self.skip)
+        self._step(None, 0.0)
 
     # -- torch.optim.Adam-compatible checkpoint layout -------------------------------------
     def state_dict(self):

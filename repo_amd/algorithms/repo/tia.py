@@ -50,6 +50,7 @@ class TIA(Dreamer):
     _BUILDS_SYMBOLIC = False       # pixel_obs=False: the state-vector modules are built for Dreamer and RePo
     _BUILDS_CONV_PRECISION = False   # conv_precision="high": built and tested for Dreamer and RePo
     _BUILDS_PCONT = False            # pcont=True: built and tested for Dreamer and RePo
+    _BUILDS_SLOW_VALUE = False       # slow_value_target=True: built and tested for Dreamer and RePo
 
     # ------------------------------------------------------------------ construction
     def build_models(self, config, env):

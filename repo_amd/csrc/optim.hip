@@ -53,6 +53,37 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(int64_t n, float* __rest
   }
 }
 
+// clip_adam_kernel's update (the same expressions, so the same bits in p, m, v) and, in the same pass, the slow target's
+// mix from the parameter value just written: t += fraction * (p_new - t); fraction == 1 stores p_new itself
+// (config.slow_value_target).  One skip word for all four buffers: they move together or not at all.
+__global__ __launch_bounds__(256) void clip_adam_target_kernel(int64_t n, float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v,
+                                                               const float* __restrict__ sqnorm, float max_norm,
+                                                               float lr_bc1, float b1, float b2, float eps,
+                                                               float inv_bc2_sqrt, const unsigned* __restrict__ skip,
+                                                               float* __restrict__ t, float fraction) {
+  if (skip && *skip) return;
+  float coef = 1.f;
+  if (sqnorm) {
+    coef = max_norm / (sqrtf(*sqnorm) + 1e-6f);
+    coef = coef > 1.f ? 1.f : coef;
+  }
+  const bool copy = fraction == 1.f;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float gg = g[i] * coef;
+    const float mm = b1 * m[i] + (1.f - b1) * gg;
+    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
+    m[i] = mm;
+    v[i] = vv;
+    const float pn = p[i] - lr_bc1 * (mm / (sqrtf(vv) * inv_bc2_sqrt + eps));
+    p[i] = pn;
+    const float tt = t[i];
+    const float d = pn - tt;
+    t[i] = copy ? pn : fmaf(fraction, d, tt);
+  }
+}
+
 }  // namespace repo
 
 using namespace repo;
@@ -91,6 +122,25 @@ extern "C" int repo_clip_adam(int64_t n, float* params, const float* grads, floa
   hipLaunchKernelGGL(clip_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, n, params, grads, exp_avg,
                      exp_avg_sq, sqnorm, max_norm, (float)((double)lr / bc1), beta1, beta2, eps,
                      (float)(1.0 / sqrt(bc2)), skip_if_nonzero);
+  REPO_CHECK_LAUNCH();
+  return REPO_OK;
+}
+
+extern "C" int repo_clip_adam_target(int64_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                     const float* sqnorm, float max_norm, float lr, float beta1, float beta2, float eps,
+                                     int64_t step, const unsigned* skip_if_nonzero, float* target, float fraction,
+                                     hipStream_t stream) {
+  REPO_ARCH_GUARD();
+  REPO_REQUIRE(n > 0 && step >= 1, REPO_E_SHAPE);
+  REPO_REQUIRE(params && grads && exp_avg && exp_avg_sq && target, REPO_E_BADARG);
+  REPO_REQUIRE(fraction > 0.f && fraction <= 1.f, REPO_E_BADARG);   // (a NaN fails both comparisons)
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  long blocks = (n + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(clip_adam_target_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, n, params, grads, exp_avg,
+                     exp_avg_sq, sqnorm, max_norm, (float)((double)lr / bc1), beta1, beta2, eps,
+                     (float)(1.0 / sqrt(bc2)), skip_if_nonzero, target, fraction);
   REPO_CHECK_LAUNCH();
   return REPO_OK;
 }

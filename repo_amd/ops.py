@@ -1119,6 +1119,19 @@ def clip_adam(p, g, m, v, sqnorm, max_norm, lr, step, betas=(0.9, 0.999), eps=1e
     )
 
 
+def clip_adam_target(p, g, m, v, sqnorm, max_norm, lr, step, target, fraction, betas=(0.9, 0.999), eps=1e-8, skip=None):
+    """clip_adam and, in the same launch, target += fraction * (p_new - target) (fraction == 1: a bit copy); a non-zero
+    `skip` word leaves all four buffers untouched (include/repo_hip.h, repo_clip_adam_target).  target: a float32 buffer
+    of p's length, updated in place."""
+    assert target.numel() == p.numel() and target.dtype == torch.float32 and target.is_contiguous()
+    check(
+        lib().repo_clip_adam_target(p.numel(), _ptr(_f32c(p)), _ptr(_f32c(g)), _ptr(_f32c(m)), _ptr(_f32c(v)),
+                                    _ptr(sqnorm), float(max_norm), float(lr), betas[0], betas[1], eps, step, _ptr(skip),
+                                    _ptr(target), float(fraction), _stream()),
+        "repo_clip_adam_target",
+    )
+
+
 def philox_normal(n, seed, offset, device):
     """The n standard normals [offset, offset+n) of Philox stream `seed` -- what a kernel given (seed, offset)
     instead of a noise tensor draws for elements 0..n-1."""
