@@ -624,6 +624,24 @@ int repo_lambda_return_disc(int64_t Hm, int64_t N, const float* rewards, const f
                             int disc_is_logit, float lambda_, float gret, float* returns, float* weights,
                             float* drewards, float* dvalues, float* ddisc, float* sums2, void* ws, size_t ws_bytes,
                             hipStream_t stream);
+/* ABI v14, addition -- the score-function (REINFORCE) actor gradient (config.actor_grad; Hafner et al. 2021:
+ * the reference has no counterpart).  Beside repo_tanh_normal_entropy, on the same reduction scheme (one thread per
+ * element, 256 per block: one launch up to 16384 elements, the follow-up launch above that, the grid-stride loop above
+ * 262144; no float atomics).  mean, std (rows, A); eps (rows, A), or NULL => drawn in-kernel, element e = row*A + a being
+ * normal number noise_offset + e (the layout of repo_rssm_imagine_fwd's eps_act: pass its (seed, offset) unchanged);
+ * returns, baseline (rows); weights (rows), or NULL for ones.  With u = fma(std, eps, mean) HELD CONSTANT (the pre-squash
+ * sample), adv = returns[row] - baseline[row], w = weights[row]:
+ *   logp_e = -0.5 eps^2 - log std - 0.5 log 2pi - 2 (log 2 - u - softplus(-2u)),   softplus(x) = max(x, 0) + log1p(exp(-|x|))
+ * -- log tanh-Normal(tanh(u)) without the atanh(tanh(u)) round trip ((u - mean)/std is eps); finite for |u| of 20 and more.
+ *   dmean[e] = gscale w adv eps / std;   dstd[e] = gscale w adv (eps^2 - 1) / std      (both or neither; the log-det term
+ *   carries no gradient);   sums2 = {sum_e w adv logp_e, sum_e logp_e}.
+ * Both noise paths feed the same float into the same expressions: equal bits.  rows <= 0, A <= 0 or rows*A >= 2^31:
+ * REPO_E_SHAPE; a NULL mean/std/returns/baseline/sums2 or only one of dmean/dstd: REPO_E_BADARG; ws_bytes below
+ * repo_reduce_workspace_bytes(): REPO_E_WS_TOO_SMALL. */
+int repo_tanh_normal_reinforce(int64_t rows, int64_t A, const float* mean, const float* std, const float* eps,
+                               uint64_t noise_seed, uint64_t noise_offset, const float* returns, const float* baseline,
+                               const float* weights, float gscale, float* dmean, float* dstd, float* sums2, void* ws,
+                               size_t ws_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------ inverse-dynamics auxiliary (ABI v10)
  * config.inv_dynamics: InverseDynamicsModel (models/utils.py:84-109) trained on DETACHED latents after every

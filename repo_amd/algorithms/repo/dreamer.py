@@ -54,6 +54,25 @@ def _as_video(frames, fps):
     return Video(frames, fps)
 
 
+ACTOR_GRADS = ("dynamics", "reinforce", "both")
+
+
+def actor_grad_mix(config):
+    """config.actor_grad / config.actor_grad_mix -> (name, m): m is the weight of the dynamics term of the
+    actor objective, 1 - m the weight of the score-function term.  "dynamics" (the default): 1; "reinforce": 0; "both":
+    actor_grad_mix (default 0.1, as in DreamerV2), read for that name only.  An unknown name, or a mix outside [0, 1] (NaN
+    included), raises ValueError."""
+    name = getattr(config, "actor_grad", "dynamics")
+    if name not in ACTOR_GRADS:
+        raise ValueError(f'actor_grad={name!r}: expected "dynamics", "reinforce" or "both"')
+    if name != "both":
+        return name, 1.0 if name == "dynamics" else 0.0
+    mix = getattr(config, "actor_grad_mix", 0.1)
+    if isinstance(mix, bool) or not isinstance(mix, (int, float, np.floating, np.integer)) or not 0.0 <= float(mix) <= 1.0:
+        raise ValueError(f"actor_grad_mix={mix!r}: expected a float in [0, 1] (the weight of the dynamics term)")
+    return name, float(mix)
+
+
 def in_conv_precision(method):
     """The agent method runs at the agent's convolution precision (config.conv_precision, ops.conv_precision): every path that
     launches conv kernels -- train_dynamics, the acting step with its graph capture, _reconstruct -- goes through this one
@@ -129,6 +148,7 @@ class Dreamer:
         self._log_pending = None     # (event, pinned host buffer, meta) of the last enqueued update
         self._pending_extra = None   # (loss sums, gradient norms) a sibling algorithm adds to the update's log
         self._pending_pcont = None   # config.pcont: the continuation head's BCE sum of the last model step
+        self._pending_rf = None      # config.actor_grad: the score-function term's two sums of the last actor-critic step
         self._log_host = torch.empty(32, dtype=torch.float32).pin_memory()
         self._act_graphs = {}
         self._act_graph_enabled = os.environ.get("REPO_ACT_GRAPH", "1") == "1"
@@ -160,6 +180,10 @@ class Dreamer:
     # config.slow_value_target = True (the lambda-returns read a slowly mixed copy of the value head): Dreamer
     # and RePo.  The sibling families bootstrap from the critic they are about to step: they refuse.
     _BUILDS_SLOW_VALUE = True
+    # config.actor_grad = "reinforce" / "both" (the score-function estimator of the actor's gradient, alone or mixed with the
+    # gradient through the imagined dynamics): Dreamer and RePo.  The sibling families train their actors
+    # through the dynamics only: they refuse anything but "dynamics".
+    _BUILDS_ACTOR_GRAD = True
 
     def build_models(self, config, env):
         self._conv_precision = getattr(config, "conv_precision", "highest")
@@ -201,6 +225,11 @@ class Dreamer:
         self._slow_value_update = int(self._slow_value_update)
         if not 0.0 < self._slow_value_fraction <= 1.0:
             raise ValueError(f"slow_value_fraction={self._slow_value_fraction!r}: expected a float in (0, 1]")
+        self._actor_grad, self._actor_mix = actor_grad_mix(config)
+        if self._actor_grad != "dynamics" and not self._BUILDS_ACTOR_GRAD:
+            raise NotImplementedError(
+                f"actor_grad={self._actor_grad!r}: {type(self).__name__} trains its actor through the imagined dynamics only; "
+                "the score-function estimator is built for Dreamer and RePo")
         obs_size = env.observation_space.shape
         action_size = int(np.prod(env.action_space.shape))
         self.action_size = action_size
@@ -656,15 +685,24 @@ class Dreamer:
             c_logit = torch.empty(Hm * N, 1, device=dev)
             _, c_hid = ops.mlp_fwd(pc, feats[:nr_], out=c_logit[:nr_], act=self.pcont_model.act)
         nv = (Hm - 1) * N
+        # config.actor_grad: m weighs the dynamics term of the actor objective, 1 - m the score-function term.
+        # Its baseline is the returns' head on the state the actor SAW at each step: slots 0..Hm-2 of the rollout, of which
+        # slots 1.. are the first rows of the values below -- so those land behind N spare rows of one buffer, and the one
+        # extra forward (the start states, N rows) fills the spare rows.
+        mix = self._actor_mix
+        v_all = torch.empty((Hm + 1) * N, 1, device=dev) if mix < 1.0 else None
+        vt_out = v_all[N:] if mix < 1.0 else None
         if self._slow_value:
             # the returns' values and bootstrap row come from the slow target on all Hm * N rows; the online head runs on
             # the rows its own loss reads
             ps, _ = self._pg(self.slow_value_model)
-            vt_pred, vt_hid = ops.mlp_fwd(ps, feats, act=act_v)
+            vt_pred, vt_hid = ops.mlp_fwd(ps, feats, out=vt_out, act=act_v)
             v_pred, v_hid = ops.mlp_fwd(pv, feats[:nv], act=act_v)
         else:
-            v_pred, v_hid = ops.mlp_fwd(pv, feats, act=act_v)
+            v_pred, v_hid = ops.mlp_fwd(pv, feats, out=vt_out, act=act_v)
             vt_pred = v_pred
+        if mix < 1.0:
+            ops.mlp_fwd(ps if self._slow_value else pv, x_all[:N], out=v_all[:N], act=act_v)
         # -- action entropy on the (attached) imagined states (dreamer.py:320-324).  The reference
         #    re-runs the actor on imag[0..Hm-1]; rows of steps 1..Hm-1 are the very inputs the rollout
         #    already pushed through the actor (detaching does not change values), so only the final
@@ -682,17 +720,28 @@ class Dreamer:
         lat_sum, dpstd = ops.normal_entropy(sv.prior_std, gscale=-c.latent_ent_coef / (Hm * gN),
                                             want_grad=c.latent_ent_coef != 0)
         # -- lambda returns and the actor objective
-        gret = -1.0 / ((Hm - 1) * gN)
+        gret = -mix / ((Hm - 1) * gN)   # (mix == 1.0: -1.0 / ..., the same bits)
+        dyn = mix > 0.0   # False: the returns take no gradient, none of their input-gradient chains is launched
         weights = None
         if self._pcont:
             # p replaces gamma in the returns, its cumulative product (held constant) weights the actor and value losses:
             # ret_sum = sum w R, and the value loss below takes the weights as its mask (its sums2[1] = sum w)
             returns, weights, dr, dv, dc, wr_sums = ops.lambda_return_disc(
-                r_pred.view(Hm, N), vt_pred.view(Hm, N), c_logit.view(Hm, N), c.gae_lambda, gret, disc_is_logit=True)
+                r_pred.view(Hm, N), vt_pred.view(Hm, N), c_logit.view(Hm, N), c.gae_lambda, gret, disc_is_logit=True,
+                want_grads=dyn)
             ret_sum, weights = wr_sums[:1], weights.view(-1)
         else:
             returns, dr, dv, ret_sum = ops.lambda_return(r_pred.view(Hm, N), vt_pred.view(Hm, N), c.gamma, c.gae_lambda,
-                                                         gret)
+                                                         gret, want_grads=dyn)
+        rf_sums = None
+        if mix < 1.0:
+            # the score-function term -(1 - m) mean(w logp adv): one streaming kernel over the rollout's own saved head
+            # outputs and action noise of steps 0..Hm-2 (a tensor, or the rollout's Philox (seed, offset) unchanged)
+            nf = (Hm - 1) * N
+            eps_rf = sv.eps_act.view(Hm * N, A)[:nf] if sv.eps_act is not None else None
+            rf_sums, dmean1, dstd1 = ops.tanh_normal_reinforce(
+                sv.a_mean[:nf], sv.a_std[:nf], eps_rf, returns.view(-1), v_all.view(-1)[:nf], weights,
+                gscale=-(1.0 - mix) / ((Hm - 1) * gN), noise=sv.noise)
         # -- backward: heads -> entropy path (input gradient only) -> reverse rollout
         #    The value head is differentiated for TWO losses on the same rows and activations: the actor's objective
         #    through the lambda-returns into the imagined states (dreamer.py:343-359, weights frozen) and the critic's
@@ -703,22 +752,26 @@ class Dreamer:
         #    With config.slow_value_target the two losses read two heads: the actor's gradient goes through the TARGET's
         #    chain into the imagined states, the critic's through the online head into its weights -- two chains by
         #    construction, and REPO_VALUE_ONE_CHAIN is not read.
-        dfeat = torch.empty(Hm * N, Fw, device=dev)
+        #    With actor_grad = "reinforce" (m = 0) nothing flows through the returns: the value / target, reward and
+        #    continuation heads' input-gradient chains are not launched, dfeat starts from zeros for the entropy path, and
+        #    the critic's chain runs in its weight-gradient-only form.
+        dfeat = torch.empty(Hm * N, Fw, device=dev) if dyn else torch.zeros(Hm * N, Fw, device=dev)
         main = torch.cuda.current_stream(dev)
         side = self._ac_side_stream or main
-        one_chain = not self._slow_value and os.environ.get("REPO_VALUE_ONE_CHAIN", "1") == "1"
-        if self._slow_value:
-            ops.mlp_bwd(ps, feats, vt_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
-        elif one_chain:
-            v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), weights, 1.0 / ((Hm - 1) * gN))
-            ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=gv, dx=dfeat, dout_w=dv2.view(nv, 1), act=act_v)
-        else:
-            ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
-        ops.mlp_bwd(pw, feats[:nr_], r_hid, dr.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_], accumulate_dx=True,
-                    act=act_w)
-        if self._pcont:   # through p inside the returns into the imagined states; the head's weights take nothing
-            ops.mlp_bwd(pc, feats[:nr_], c_hid, dc.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_], accumulate_dx=True,
-                        act=self.pcont_model.act)
+        one_chain = dyn and not self._slow_value and os.environ.get("REPO_VALUE_ONE_CHAIN", "1") == "1"
+        if dyn:
+            if self._slow_value:
+                ops.mlp_bwd(ps, feats, vt_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
+            elif one_chain:
+                v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), weights, 1.0 / ((Hm - 1) * gN))
+                ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=gv, dx=dfeat, dout_w=dv2.view(nv, 1), act=act_v)
+            else:
+                ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
+            ops.mlp_bwd(pw, feats[:nr_], r_hid, dr.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_], accumulate_dx=True,
+                        act=act_w)
+            if self._pcont:   # through p inside the returns into the imagined states; the head's weights take nothing
+                ops.mlp_bwd(pc, feats[:nr_], c_hid, dc.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_],
+                            accumulate_dx=True, act=self.pcont_model.act)
         # -- the critic's step (one chain: only the optimiser step is left of it), forked onto a side stream: it runs
         #    while the reverse rollout (which fills only ~77 CUs) and the actor backward proceed on the main stream
         side.wait_stream(main)  # after the value head's backward above read the weights
@@ -740,6 +793,9 @@ class Dreamer:
                              a_min_std=a_consts[0], a_mean_scale=a_consts[2], d_araw=d_out)
         ops.actor_head_bwd(mean2, std2, dmean=dmean2, dstd=dstd2, min_std=a_consts[0], mean_scale=a_consts[2],
                            out=d_out[ent_rows], accumulate=True)
+        if mix < 1.0:   # the score-function term reaches the actor only: onto the rows the reverse rollout has written
+            ops.actor_head_bwd(sv.a_mean[:nf], sv.a_std[:nf], dmean=dmean1, dstd=dstd1, min_std=a_consts[0],
+                               mean_scale=a_consts[2], out=d_out[:nf], accumulate=True)
         # -- ONE actor-trunk backward over every row the actor saw: both gradient paths share the
         #    same forward activations, and the chain is linear in the output gradient
         ops.mlp_bwd(pa, x_all, [sv.a_hidden[l] for l in range(nl)], d_out, dparams=ga, accumulate_w=False, dx=None,
@@ -753,6 +809,7 @@ class Dreamer:
         self.actor_optimizer.clip_and_step(c.grad_clip_norm)
         main.wait_stream(side)
         self._pending_ac = (ret_sum, ent_sum, lat_sum, v_sums, Hm, gN)
+        self._pending_rf = rf_sums
         self._log_update()
 
     # ------------------------------------------------------------------ logging: one D2H per update
@@ -779,6 +836,10 @@ class Dreamer:
             pcs, self._pending_pcont = self._pending_pcont, None
             pcs.record_stream(cur)
             xs = torch.cat([xs, pcs])
+        if self._actor_mix < 1.0:   # config.actor_grad: [sum w adv logp, sum logp], behind pcont's
+            rfs, self._pending_rf = self._pending_rf, None
+            rfs.record_stream(cur)
+            xs = torch.cat([xs, rfs])
         parts = [msc[:4], ret_sum, ent_sum, lat_sum, v_sums, xs, msc[4:5], self.actor_optimizer.sqnorm,
                  self.value_optimizer.sqnorm, xn]
         if dual is not None:
@@ -837,6 +898,9 @@ class Dreamer:
         else:
             out["train/kl_loss"] = kl / grow
         out["train/model_loss"] = out["train/obs_loss"] + out["train/reward_loss"] + out["train/kl_loss"]
+        rf = None
+        if self._actor_mix < 1.0:   # [.., sum w adv logp, sum logp] (see _log_update)
+            xsums, rf = xsums[:-2], xsums[-2:]
         if self._pcont:   # [.., BCE sum] (see _log_update)
             xsums, pc_sum = xsums[:-1], xsums[-1]
             out["train/pcont_loss"] = self._pcont_scale * pc_sum / grow
@@ -844,6 +908,10 @@ class Dreamer:
         self._extra_scalars(out, xsums, xnorms, grow)
         action_entropy = ent / (Hm * gN)
         latent_entropy = lat / (Hm * gN) + self._LATENT_ENTROPY_SHIFT * self.c.state_size
+        if rf is not None:   # -mean(w (m R + (1 - m) logp adv)) over the (Hm - 1) * gN rows
+            m = self._actor_mix
+            ret = m * ret + (1.0 - m) * rf[0]
+            out["train/actor_logprob"] = rf[1] / ((Hm - 1) * gN)
         out["train/actor_loss"] = (-ret / ((Hm - 1) * gN) - c.action_ent_coef * action_entropy
                                    - c.latent_ent_coef * latent_entropy)
         if self._pcont:   # ret = sum w R, _vn = sum w: the weighted means over the (Hm - 1) * gN elements

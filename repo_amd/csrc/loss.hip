@@ -199,6 +199,54 @@ __global__ __launch_bounds__(256) void tanh_normal_entropy_kernel(int n, int NS,
   last_block_finishes(parts, 1, red_out, ticket, red);
 }
 
+// ------------------------------------------------------------------ score-function (REINFORCE) actor term
+// u = fma(std, eps, mean), held constant (the pre-squash sample of the rollout); per element e = row*A + a
+//   logp_e = -0.5 eps^2 - log std - 0.5 log 2pi - 2 (log 2 - u - softplus(-2u))
+// ((u - mean)/std is eps itself; no atanh(tanh(u)) round trip), softplus(x) = max(x, 0) + log1p(exp(-|x|)): exp only ever
+// sees a non-positive argument.  With adv = returns[row] - baseline[row], w = weights[row] (null: 1):
+//   dmean[e] = gscale w adv eps / std ;  dstd[e] = gscale w adv (eps^2 - 1) / std      (the log-det term carries no gradient)
+//   parts[0][blk] = sum_e w adv logp_e ;  parts[1][blk] = sum_e logp_e
+// eps null: element e is normal number noffset + e of the Philox stream -- the rollout's own layout of eps_act.
+// libm's expf / log1pf / logf: a streaming kernel, its loads bound it.
+__global__ __launch_bounds__(256) void tanh_normal_reinforce_kernel(int n, int A, const float* __restrict__ mean,
+                                                                    const float* __restrict__ stdv,
+                                                                    const float* __restrict__ eps, uint64_t nseed,
+                                                                    uint64_t noffset, const float* __restrict__ returns,
+                                                                    const float* __restrict__ baseline,
+                                                                    const float* __restrict__ weights, float gscale,
+                                                                    float* __restrict__ dmean, float* __restrict__ dstd,
+                                                                    float* __restrict__ parts, float* __restrict__ red_out,
+    unsigned* __restrict__ ticket) {
+  __shared__ float red[16];
+  const float kLog2 = 0.69314718055994531f;
+  float awl = 0.f, al = 0.f;
+  // (a 64-bit loop counter: n may be within one grid stride of 2^31)
+  for (long e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+    const int row = (int)e / A;
+    const float mu = mean[e], sd = stdv[e];
+    const float ep = eps ? eps[e] : philox_normal(nseed, noffset + (uint64_t)e);
+    const float wa = (weights ? weights[row] : 1.f) * (returns[row] - baseline[row]);
+    const float u = fmaf(sd, ep, mu);
+    const float x = -2.f * u;
+    const float sp = fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));
+    const float lp = -0.5f * ep * ep - logf(sd) - 0.5f * kLog2Pi - 2.f * (kLog2 - u - sp);
+    awl += wa * lp;
+    al += lp;
+    if (dmean) {
+      const float g = gscale * wa / sd;
+      dmean[e] = g * ep;
+      dstd[e] = g * (ep * ep - 1.f);
+    }
+  }
+  const float s0 = block_sum(awl, red);
+  const float s1 = block_sum(al, red);
+  if (threadIdx.x == 0) {
+    parts[blockIdx.x] = s0;
+    parts[gridDim.x + blockIdx.x] = s1;
+  }
+  last_block_finishes(parts, 2, red_out, ticket, red);
+}
+
 // sum over elements of (0.5 + 0.5 log 2pi + log std); dstd = gscale / std   (dreamer.py:327-328)
 __global__ __launch_bounds__(256) void normal_entropy_kernel(int n, const float* __restrict__ stdv, float gscale,
                                                              float* __restrict__ dstd, float* __restrict__ parts, float* __restrict__ red_out,
@@ -592,7 +640,24 @@ extern "C" int repo_tanh_normal_entropy(int64_t rows, int64_t A, int64_t samples
   return red_finish(ws, blocks, 1, ent_sum, stream);
 }
 
-extern "C" int repo_normal_entropy(int64_t n, const float* std, float gscale, float* dstd, float* ent_sum, void* ws,
+extern "C" int repo_tanh_normal_reinforce(int64_t rows, int64_t A, const float* mean, const float* std, const float* eps,
+                                          uint64_t noise_seed, uint64_t noise_offset, const float* returns,
+                                          const float* baseline, const float* weights, float gscale, float* dmean,
+                                          float* dstd, float* sums2, void* ws, size_t ws_bytes, hipStream_t stream) {
+  REPO_ARCH_GUARD();
+  REPO_REQUIRE(rows > 0 && A > 0 && rows < kMaxIdx && A < kMaxIdx && rows * A < kMaxIdx, REPO_E_SHAPE);
+  REPO_REQUIRE(mean && std && returns && baseline && sums2 && ((dmean == nullptr) == (dstd == nullptr)), REPO_E_BADARG);
+  REPO_REQUIRE(ws && ws_bytes >= repo_reduce_workspace_bytes(), REPO_E_WS_TOO_SMALL);
+  const long n = rows * A;
+  const int blocks = red_blocks(n, 256);
+  hipLaunchKernelGGL(tanh_normal_reinforce_kernel, dim3(blocks), dim3(256), 0, stream, (int)n, (int)A, mean, std, eps,
+                     noise_seed, noise_offset, returns, baseline, weights, gscale, dmean, dstd, red_parts(ws), sums2,
+                     red_ticket(ws, blocks));
+  REPO_CHECK_LAUNCH();
+  return red_finish(ws, blocks, 2, sums2, stream);
+}
+
+extern "C" int repo_normal_entropy(int64_t n,const float* std, float gscale, float* dstd, float* ent_sum, void* ws,
                                    size_t ws_bytes, hipStream_t stream) {
   REPO_ARCH_GUARD();
   REPO_REQUIRE(n > 0 && n < kMaxIdx, REPO_E_SHAPE);

@@ -1017,6 +1017,30 @@ def tanh_normal_entropy(mean, std, eps, gscale=0.0, want_grads=True, noise=(0, 0
     return out, dmean, dstd
 
 
+def tanh_normal_reinforce(mean, std, eps, returns, baseline, weights=None, gscale=0.0, want_grads=True, noise=(0, 0)):
+    """The score-function actor term (include/repo_hip.h, repo_tanh_normal_reinforce).  mean, std (rows, A); eps (rows, A),
+    or None: element e is normal number noise[1] + e of Philox stream noise[0]; returns, baseline (rows,); weights (rows,)
+    or None for ones.  -> (sums2 = [sum w adv logp, sum logp], dmean, dstd (rows, A) or None)."""
+    rows, A = mean.shape
+    dev = mean.device
+    assert std.shape == mean.shape and returns.numel() == rows and baseline.numel() == rows
+    assert eps is None or eps.numel() == rows * A
+    assert weights is None or weights.numel() == rows
+    dmean = torch.empty(rows, A, dtype=torch.float32, device=dev) if want_grads else None
+    dstd = torch.empty(rows, A, dtype=torch.float32, device=dev) if want_grads else None
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = reduce_ws(dev)
+    check(
+        lib().repo_tanh_normal_reinforce(rows, A, _ptr(_f32c(mean)), _ptr(_f32c(std)),
+                                         _ptr(_f32c(eps)) if eps is not None else None, int(noise[0]), int(noise[1]),
+                                         _ptr(_f32c(returns)), _ptr(_f32c(baseline)),
+                                         _ptr(_f32c(weights)) if weights is not None else None, float(gscale),
+                                         _ptr(dmean), _ptr(dstd), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+        "repo_tanh_normal_reinforce",
+    )
+    return out, dmean, dstd
+
+
 def tanh_normal_mode(mean, std, eps):
     rows, A = mean.shape
     action = torch.empty_like(mean)
