@@ -642,6 +642,41 @@ int repo_tanh_normal_reinforce(int64_t rows, int64_t A, const float* mean, const
                                uint64_t noise_seed, uint64_t noise_offset, const float* returns, const float* baseline,
                                const float* weights, float gscale, float* dmean, float* dstd, float* sums2, void* ws,
                                size_t ws_bytes, hipStream_t stream);
+/* ABI v14, additions -- return normalisation (config.return_norm; Hafner et al. 2023: the reference has no
+ * counterpart).  The returns term of the actor objective is divided by max(limit, S), S a running average of the spread
+ * between two order statistics of the imagined lambda-returns -- selected, averaged and inverted on the device, and carried
+ * into the gradients as a device scalar, so that the update reads nothing back.
+ *
+ * repo_return_scale: x (n) fp32, any values.  lo_b / hi_b = the k_lo-th / k_hi-th smallest element of x (0-based), EXACT: a
+ * radix select over order-preserving keys of the fp32 bits (-0 and +0 compare equal and come back as +0, every NaN sorts
+ * behind +inf and comes back as a quiet NaN), integer counts only -- the result does not depend on the schedule, two runs agree
+ * in bits.  One workgroup of repo_return_scale_geometry()'s `threads` walks x four times (one pass per 8-bit digit),
+ * `per_trip` elements per trip of the walk; it ends on any input.  Then, by one thread, with state2 = {lo, hi}:
+ *   ok = lo_b and hi_b finite and not (skip_if_nonzero && *skip_if_nonzero)       (a NaN must never enter the average)
+ *   ok and update_state:  lo <- fmaf(decay, lo, (1 - decay) lo_b),  hi likewise,  written back to state2
+ *   scale = max(limit, hi - lo);   out4 = {lo_b, hi_b, scale, 1 / scale}           (every element, always)
+ * so update_state = 0, a faulted update (the skip word of repo_dual_step / repo_clip_adam) and a non-finite statistic all
+ * leave state2's bits alone and form the scale from it as it is.  n <= 0, n >= 2^31, k_lo < 0, k_hi >= n or k_lo > k_hi:
+ * REPO_E_SHAPE; a NULL x / state2 / out4: REPO_E_BADARG; ws NULL or ws_bytes below repo_reduce_workspace_bytes():
+ * REPO_E_WS_TOO_SMALL (the reduction workspace's contract, zeroed header and one per stream, is kept for a
+ * several-workgroup form behind this signature; the one-workgroup kernel does not touch it).
+ * repo_return_scale_finish: the same epilogue on batch2 = {lo_b, hi_b} given (a data-parallel job averages the ranks'
+ * statistics between a repo_return_scale(update_state = 0) and this call).  NULL batch2 / state2 / out4: REPO_E_BADARG.
+ * repo_scale_by: a[i] *= *gmul, and b[i], c[i] where given (n elements each) -- gradients that are linear in a by-value
+ * scale and were formed before the device scalar existed.  n <= 0 or n >= 2^31: REPO_E_SHAPE; NULL a / gmul: REPO_E_BADARG.
+ * repo_tanh_normal_reinforce_gmul: repo_tanh_normal_reinforce with gscale * *gmul in place of gscale (gmul NULL: the very
+ * kernel of repo_tanh_normal_reinforce, the same bits; the sums do not depend on either). */
+int repo_return_scale_geometry(int* threads, int* per_trip);
+int repo_return_scale(int64_t n, const float* x, int64_t k_lo, int64_t k_hi, float decay, float limit, float* state2,
+                      float* out4, int update_state, const unsigned* skip_if_nonzero, void* ws, size_t ws_bytes,
+                      hipStream_t stream);
+int repo_return_scale_finish(const float* batch2, float decay, float limit, float* state2, float* out4, int update_state,
+                             const unsigned* skip_if_nonzero, hipStream_t stream);
+int repo_scale_by(int64_t n, float* a, float* b, float* c, const float* gmul, hipStream_t stream);
+int repo_tanh_normal_reinforce_gmul(int64_t rows, int64_t A, const float* mean, const float* std, const float* eps,
+                                    uint64_t noise_seed, uint64_t noise_offset, const float* returns, const float* baseline,
+                                    const float* weights, float gscale, const float* gmul, float* dmean, float* dstd,
+                                    float* sums2, void* ws, size_t ws_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------ inverse-dynamics auxiliary (ABI v10)
  * config.inv_dynamics: InverseDynamicsModel (models/utils.py:84-109) trained on DETACHED latents after every

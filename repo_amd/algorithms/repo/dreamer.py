@@ -73,6 +73,30 @@ def actor_grad_mix(config):
     return name, float(mix)
 
 
+def return_norm_config(config):
+    """config.return_norm and its four keys -> (on, decay, low, high, limit).  return_norm_decay (default
+    0.99) in [0, 1); 0 <= return_norm_low (0.05) < return_norm_high (0.95) <= 1; return_norm_limit (1.0) > 0.  A value
+    outside its range (NaN included) raises ValueError, whether the feature is on or not."""
+    def num(key, default):
+        v = getattr(config, key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+            raise ValueError(f"{key}={v!r}: expected a number")
+        return float(v)
+
+    on = getattr(config, "return_norm", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"return_norm={on!r}: expected True or False")
+    decay, low, high = num("return_norm_decay", 0.99), num("return_norm_low", 0.05), num("return_norm_high", 0.95)
+    limit = num("return_norm_limit", 1.0)
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"return_norm_decay={decay!r}: expected a float in [0, 1)")
+    if not 0.0 <= low < high <= 1.0:
+        raise ValueError(f"return_norm_low={low!r}, return_norm_high={high!r}: expected 0 <= low < high <= 1")
+    if not (limit > 0.0 and math.isfinite(limit)):
+        raise ValueError(f"return_norm_limit={limit!r}: expected a finite float > 0")
+    return bool(on), decay, low, high, limit
+
+
 def in_conv_precision(method):
     """The agent method runs at the agent's convolution precision (config.conv_precision, ops.conv_precision): every path that
     launches conv kernels -- train_dynamics, the acting step with its graph capture, _reconstruct -- goes through this one
@@ -149,6 +173,7 @@ class Dreamer:
         self._pending_extra = None   # (loss sums, gradient norms) a sibling algorithm adds to the update's log
         self._pending_pcont = None   # config.pcont: the continuation head's BCE sum of the last model step
         self._pending_rf = None      # config.actor_grad: the score-function term's two sums of the last actor-critic step
+        self._pending_rn = None      # config.return_norm: [scale, 1 / scale, lo, hi] of the last actor-critic step
         self._log_host = torch.empty(32, dtype=torch.float32).pin_memory()
         self._act_graphs = {}
         self._act_graph_enabled = os.environ.get("REPO_ACT_GRAPH", "1") == "1"
@@ -184,6 +209,9 @@ class Dreamer:
     # gradient through the imagined dynamics): Dreamer and RePo.  The sibling families train their actors
     # through the dynamics only: they refuse anything but "dynamics".
     _BUILDS_ACTOR_GRAD = True
+    # config.return_norm = True (the returns term of the actor objective divided by the running percentile range of the
+    # imagined returns): Dreamer and RePo.  The sibling families keep the raw returns: they refuse.
+    _BUILDS_RETURN_NORM = True
 
     def build_models(self, config, env):
         self._conv_precision = getattr(config, "conv_precision", "highest")
@@ -230,6 +258,11 @@ class Dreamer:
             raise NotImplementedError(
                 f"actor_grad={self._actor_grad!r}: {type(self).__name__} trains its actor through the imagined dynamics only; "
                 "the score-function estimator is built for Dreamer and RePo")
+        (self._return_norm, self._rn_decay, self._rn_low, self._rn_high, self._rn_limit) = return_norm_config(config)
+        if self._return_norm and not self._BUILDS_RETURN_NORM:
+            raise NotImplementedError(
+                f"return_norm=True: {type(self).__name__} weighs its actor objective in raw reward units; return "
+                "normalisation is built for Dreamer and RePo")
         obs_size = env.observation_space.shape
         action_size = int(np.prod(env.action_space.shape))
         self.action_size = action_size
@@ -246,6 +279,8 @@ class Dreamer:
         self._build_optimizers(config)
         if self._slow_value:
             self._build_slow_value(config)
+        if self._return_norm:
+            self._build_return_norm()
         if self._inv_dyn:
             # behind the value model, as the reference constructs it (dreamer.py:130-141) => same default init under a seed
             self.inv_dynamics = InverseDynamicsModel(
@@ -322,6 +357,11 @@ class Dreamer:
             q.data = self._slow_value_flat[o : o + q.numel()].view(q.shape)
         assert [tuple(q.shape) for q in self.slow_value_model.plist()] == [tuple(q.shape) for q in opt.params]
         opt.track_target(self._slow_value_flat, self._slow_value_update, self._slow_value_fraction)
+
+    def _build_return_norm(self):
+        """config.return_norm: the running low / high order statistics of the imagined returns, two floats
+        on the device, zeros at construction (checkpoint key "return_norm").  Only repo_return_scale writes them."""
+        self._return_state = torch.zeros(2, dtype=torch.float32, device=self.device)
 
     def _wgrad_side(self, batch):
         """The weight-gradient side stream for a batch of `batch` sequences, or None (in line)."""
@@ -733,6 +773,28 @@ class Dreamer:
         else:
             returns, dr, dv, ret_sum = ops.lambda_return(r_pred.view(Hm, N), vt_pred.view(Hm, N), c.gamma, c.gae_lambda,
                                                          gret, want_grads=dyn)
+        rn_inv = None
+        if self._return_norm:
+            # config.return_norm: two order statistics of the returns as the kernel above wrote them, the
+            # running range, and inv = 1 / max(limit, range) as a DEVICE scalar -- the gradients that are linear in gret were
+            # formed before it existed and are scaled in place, the score-function kernel below multiplies its gscale
+            nret = (Hm - 1) * N
+            k_lo, k_hi = ops.return_ranks(nret, self._rn_low, self._rn_high)
+            if self.dp is None:
+                rn = ops.return_scale(returns, k_lo, k_hi, self._rn_decay, self._rn_limit, self._return_state,
+                                      skip=self._ustatus)
+            else:   # the ranks' statistics are averaged ahead of the running average: one collective of two floats
+                rn = ops.return_scale(returns, k_lo, k_hi, self._rn_decay, self._rn_limit, self._return_state,
+                                      update_state=False)
+                stat = rn[:2].clone()
+                self._allreduce(stat)
+                stat /= self.dp.world_size
+                rn = ops.return_scale_finish(stat, self._rn_decay, self._rn_limit, self._return_state,
+                                             skip=self._ustatus, out=rn)
+            rn_inv = rn[3:4]
+            if dyn:
+                ops.scale_by(rn_inv, dr, dv, dc if self._pcont else None)
+            self._pending_rn = torch.cat([rn[2:4], self._return_state])
         rf_sums = None
         if mix < 1.0:
             # the score-function term -(1 - m) mean(w logp adv): one streaming kernel over the rollout's own saved head
@@ -741,7 +803,7 @@ class Dreamer:
             eps_rf = sv.eps_act.view(Hm * N, A)[:nf] if sv.eps_act is not None else None
             rf_sums, dmean1, dstd1 = ops.tanh_normal_reinforce(
                 sv.a_mean[:nf], sv.a_std[:nf], eps_rf, returns.view(-1), v_all.view(-1)[:nf], weights,
-                gscale=-(1.0 - mix) / ((Hm - 1) * gN), noise=sv.noise)
+                gscale=-(1.0 - mix) / ((Hm - 1) * gN), noise=sv.noise, gmul=rn_inv)
         # -- backward: heads -> entropy path (input gradient only) -> reverse rollout
         #    The value head is differentiated for TWO losses on the same rows and activations: the actor's objective
         #    through the lambda-returns into the imagined states (dreamer.py:343-359, weights frozen) and the critic's
@@ -840,6 +902,10 @@ class Dreamer:
             rfs, self._pending_rf = self._pending_rf, None
             rfs.record_stream(cur)
             xs = torch.cat([xs, rfs])
+        if self._return_norm:   # config.return_norm: [scale, 1 / scale, lo, hi] -- no sums, the same on every rank: they
+            rns, self._pending_rn = self._pending_rn, None   # ride behind the extra gradient norms, which are not summed
+            rns.record_stream(cur)
+            xn = torch.cat([xn, rns])
         parts = [msc[:4], ret_sum, ent_sum, lat_sum, v_sums, xs, msc[4:5], self.actor_optimizer.sqnorm,
                  self.value_optimizer.sqnorm, xn]
         if dual is not None:
@@ -889,6 +955,9 @@ class Dreamer:
         xsums, h = h[9 : 9 + nxs], h[:9] + h[9 + nxs :]
         gm, ga_, gv_ = h[9:12]
         xnorms, h = h[12 : 12 + nxn], h[:12] + h[12 + nxn :]
+        rn = None
+        if self._return_norm:   # [.., scale, 1 / scale, lo, hi] (see _log_update)
+            xnorms, rn = xnorms[:-4], xnorms[-4:]
         npix = self._npix
         out = {}
         out["train/obs_loss"] = nll / grow + 0.5 * LOG_2PI * npix
@@ -912,6 +981,9 @@ class Dreamer:
             m = self._actor_mix
             ret = m * ret + (1.0 - m) * rf[0]
             out["train/actor_logprob"] = rf[1] / ((Hm - 1) * gN)
+        if rn is not None:   # the returns term as the actor was trained on it: times the 1 / scale that rode in the copy
+            ret = ret * rn[1]
+            out["train/return_scale"], out["train/return_lo"], out["train/return_hi"] = rn[0], rn[2], rn[3]
         out["train/actor_loss"] = (-ret / ((Hm - 1) * gN) - c.action_ent_coef * action_entropy
                                    - c.latent_ent_coef * latent_entropy)
         if self._pcont:   # ret = sum w R, _vn = sum w: the weighted means over the (Hm - 1) * gN elements
@@ -1165,6 +1237,8 @@ class Dreamer:
             params["pcont_model"] = sd(self.pcont_model)
         if self._slow_value:   # the value head's key names; its phase is value_optimizer's step count
             params["slow_value_model"] = sd(self.slow_value_model)
+        if self._return_norm:   # the running low / high order statistics of the imagined returns
+            params["return_norm"] = self._return_state.detach().clone()
         if self._inv_dyn:   # dreamer.py:517-519
             params["inv_dynamics"] = sd(self.inv_dynamics)
             params["inv_dynamics_optimizer"] = self.inv_dynamics_optimizer.state_dict()
@@ -1207,6 +1281,8 @@ class Dreamer:
                 self._load_module(self.slow_value_model, params["slow_value_model"])
             else:   # a checkpoint written with the key off: the hard update at step 0, from the head just loaded
                 self._slow_value_flat.copy_(self.value_optimizer.flat)
+        if self._return_norm and "return_norm" in params:   # (a checkpoint written with the key off: the state stays)
+            self._return_state.copy_(params["return_norm"].to(self.device, torch.float32).reshape(2))
         if self._inv_dyn and "inv_dynamics" in params:   # a checkpoint without them loads (dreamer.py:560-564)
             self._load_module(self.inv_dynamics, params["inv_dynamics"])
             self.inv_dynamics_optimizer.load_state_dict(params["inv_dynamics_optimizer"])

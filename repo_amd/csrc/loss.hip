@@ -208,17 +208,22 @@ __global__ __launch_bounds__(256) void tanh_normal_entropy_kernel(int n, int NS,
 //   parts[0][blk] = sum_e w adv logp_e ;  parts[1][blk] = sum_e logp_e
 // eps null: element e is normal number noffset + e of the Philox stream -- the rollout's own layout of eps_act.
 // libm's expf / log1pf / logf: a streaming kernel, its loads bound it.
+// GMUL (config.return_norm): gscale is multiplied by the device scalar *gmul first; without it the multiply is
+// not in the kernel and the gradients keep their bits.
+template <bool GMUL>
 __global__ __launch_bounds__(256) void tanh_normal_reinforce_kernel(int n, int A, const float* __restrict__ mean,
                                                                     const float* __restrict__ stdv,
                                                                     const float* __restrict__ eps, uint64_t nseed,
                                                                     uint64_t noffset, const float* __restrict__ returns,
                                                                     const float* __restrict__ baseline,
                                                                     const float* __restrict__ weights, float gscale,
+                                                                    const float* __restrict__ gmul,
                                                                     float* __restrict__ dmean, float* __restrict__ dstd,
                                                                     float* __restrict__ parts, float* __restrict__ red_out,
     unsigned* __restrict__ ticket) {
   __shared__ float red[16];
   const float kLog2 = 0.69314718055994531f;
+  if constexpr (GMUL) gscale *= *gmul;
   float awl = 0.f, al = 0.f;
   // (a 64-bit loop counter: n may be within one grid stride of 2^31)
   for (long e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
@@ -640,21 +645,38 @@ extern "C" int repo_tanh_normal_entropy(int64_t rows, int64_t A, int64_t samples
   return red_finish(ws, blocks, 1, ent_sum, stream);
 }
 
-extern "C" int repo_tanh_normal_reinforce(int64_t rows, int64_t A, const float* mean, const float* std, const float* eps,
-                                          uint64_t noise_seed, uint64_t noise_offset, const float* returns,
-                                          const float* baseline, const float* weights, float gscale, float* dmean,
-                                          float* dstd, float* sums2, void* ws, size_t ws_bytes, hipStream_t stream) {
+static int tanh_normal_reinforce(int64_t rows, int64_t A, const float* mean, const float* std, const float* eps,
+                                uint64_t noise_seed, uint64_t noise_offset, const float* returns, const float* baseline,
+                                const float* weights, float gscale, const float* gmul, float* dmean, float* dstd,
+                                float* sums2, void* ws, size_t ws_bytes, hipStream_t stream) {
   REPO_ARCH_GUARD();
   REPO_REQUIRE(rows > 0 && A > 0 && rows < kMaxIdx && A < kMaxIdx && rows * A < kMaxIdx, REPO_E_SHAPE);
   REPO_REQUIRE(mean && std && returns && baseline && sums2 && ((dmean == nullptr) == (dstd == nullptr)), REPO_E_BADARG);
   REPO_REQUIRE(ws && ws_bytes >= repo_reduce_workspace_bytes(), REPO_E_WS_TOO_SMALL);
   const long n = rows * A;
   const int blocks = red_blocks(n, 256);
-  hipLaunchKernelGGL(tanh_normal_reinforce_kernel, dim3(blocks), dim3(256), 0, stream, (int)n, (int)A, mean, std, eps,
-                     noise_seed, noise_offset, returns, baseline, weights, gscale, dmean, dstd, red_parts(ws), sums2,
-                     red_ticket(ws, blocks));
+  auto kern = gmul ? tanh_normal_reinforce_kernel<true> : tanh_normal_reinforce_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, stream, (int)n, (int)A, mean, std, eps, noise_seed, noise_offset,
+                     returns, baseline, weights, gscale, gmul, dmean, dstd, red_parts(ws), sums2, red_ticket(ws, blocks));
   REPO_CHECK_LAUNCH();
   return red_finish(ws, blocks, 2, sums2, stream);
+}
+
+extern "C" int repo_tanh_normal_reinforce(int64_t rows, int64_t A, const float* mean, const float* std, const float* eps,
+                                          uint64_t noise_seed, uint64_t noise_offset, const float* returns,
+                                          const float* baseline, const float* weights, float gscale, float* dmean,
+                                          float* dstd, float* sums2, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return tanh_normal_reinforce(rows, A, mean, std, eps, noise_seed, noise_offset, returns, baseline, weights, gscale,
+                               nullptr, dmean, dstd, sums2, ws, ws_bytes, stream);
+}
+
+extern "C" int repo_tanh_normal_reinforce_gmul(int64_t rows, int64_t A, const float* mean, const float* std,
+                                               const float* eps, uint64_t noise_seed, uint64_t noise_offset,
+                                               const float* returns, const float* baseline, const float* weights,
+                                               float gscale, const float* gmul, float* dmean, float* dstd, float* sums2,
+                                               void* ws, size_t ws_bytes, hipStream_t stream) {
+  return tanh_normal_reinforce(rows, A, mean, std, eps, noise_seed, noise_offset, returns, baseline, weights, gscale, gmul,
+                               dmean, dstd, sums2, ws, ws_bytes, stream);
 }
 
 extern "C" int repo_normal_entropy(int64_t n,const float* std, float gscale, float* dstd, float* ent_sum, void* ws,

@@ -6,6 +6,7 @@ used for device memory and streams only -- there is no eager/CPU fallback here: 
 library or a CPU tensor raises.
 """
 import contextlib
+import math
 import os
 import threading
 
@@ -1017,10 +1018,12 @@ def tanh_normal_entropy(mean, std, eps, gscale=0.0, want_grads=True, noise=(0, 0
     return out, dmean, dstd
 
 
-def tanh_normal_reinforce(mean, std, eps, returns, baseline, weights=None, gscale=0.0, want_grads=True, noise=(0, 0)):
+def tanh_normal_reinforce(mean, std, eps, returns, baseline, weights=None, gscale=0.0, want_grads=True, noise=(0, 0),
+                          gmul=None):
     """The score-function actor term (include/repo_hip.h, repo_tanh_normal_reinforce).  mean, std (rows, A); eps (rows, A),
     or None: element e is normal number noise[1] + e of Philox stream noise[0]; returns, baseline (rows,); weights (rows,)
-    or None for ones.  -> (sums2 = [sum w adv logp, sum logp], dmean, dstd (rows, A) or None)."""
+    or None for ones; gmul: a one-element device tensor that multiplies gscale (repo_tanh_normal_reinforce_gmul), or None.
+    -> (sums2 = [sum w adv logp, sum logp], dmean, dstd (rows, A) or None)."""
     rows, A = mean.shape
     dev = mean.device
     assert std.shape == mean.shape and returns.numel() == rows and baseline.numel() == rows
@@ -1030,6 +1033,18 @@ def tanh_normal_reinforce(mean, std, eps, returns, baseline, weights=None, gscal
     dstd = torch.empty(rows, A, dtype=torch.float32, device=dev) if want_grads else None
     out = torch.empty(2, dtype=torch.float32, device=dev)
     ws = reduce_ws(dev)
+    if gmul is not None:
+        assert gmul.numel() == 1
+        check(
+            lib().repo_tanh_normal_reinforce_gmul(rows, A, _ptr(_f32c(mean)), _ptr(_f32c(std)),
+                                                  _ptr(_f32c(eps)) if eps is not None else None, int(noise[0]),
+                                                  int(noise[1]), _ptr(_f32c(returns)), _ptr(_f32c(baseline)),
+                                                  _ptr(_f32c(weights)) if weights is not None else None, float(gscale),
+                                                  _ptr(_f32c(gmul)), _ptr(dmean), _ptr(dstd), _ptr(out), _ptr(ws),
+                                                  ws.numel(), _stream()),
+            "repo_tanh_normal_reinforce_gmul",
+        )
+        return out, dmean, dstd
     check(
         lib().repo_tanh_normal_reinforce(rows, A, _ptr(_f32c(mean)), _ptr(_f32c(std)),
                                          _ptr(_f32c(eps)) if eps is not None else None, int(noise[0]), int(noise[1]),
@@ -1121,6 +1136,61 @@ def lambda_return_disc(rewards, values, disc, lambda_, gret=0.0, disc_is_logit=F
         "repo_lambda_return_disc",
     )
     return returns, weights, dr, dv, dd, out
+
+
+def return_ranks(n, low, high):
+    """The 0-based ranks of the two order statistics of n values: floor(low (n - 1)), ceil(high (n - 1))."""
+    return int(math.floor(low * (n - 1))), int(math.ceil(high * (n - 1)))
+
+
+def return_scale_geometry():
+    """(threads, elements per trip) of repo_return_scale's one workgroup: the sizes at which its walk changes regime."""
+    t, e = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().repo_return_scale_geometry(ctypes.addressof(t), ctypes.addressof(e)), "repo_return_scale_geometry")
+    return t.value, e.value
+
+
+def return_scale(x, k_lo, k_hi, decay, limit, state, update_state=True, skip=None, out=None):
+    """Two exact order statistics of x and the running percentile range (include/repo_hip.h, repo_return_scale).  x: any
+    shape, fp32; state (2,) = [lo, hi], updated in place unless update_state is False, the skip word (int32 device tensor)
+    is non-zero or a statistic is not finite.  -> out (4,) = [lo_b, hi_b, scale, 1 / scale]."""
+    dev = x.device
+    assert state.numel() == 2
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+    ws = reduce_ws(dev)
+    check(
+        lib().repo_return_scale(x.numel(), _ptr(_f32c(x)), int(k_lo), int(k_hi), float(decay), float(limit),
+                                _ptr(_f32c(state)), _ptr(_f32c(out)), int(bool(update_state)), _ptr(skip), _ptr(ws),
+                                ws.numel(), _stream()),
+        "repo_return_scale",
+    )
+    return out
+
+
+def return_scale_finish(batch, decay, limit, state, update_state=True, skip=None, out=None):
+    """repo_return_scale's epilogue on given statistics batch (2,) = [lo_b, hi_b] (include/repo_hip.h): the guard, the
+    running average in state (2,), -> out (4,) = [lo_b, hi_b, scale, 1 / scale]."""
+    assert batch.numel() == 2 and state.numel() == 2
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=batch.device)
+    check(
+        lib().repo_return_scale_finish(_ptr(_f32c(batch)), float(decay), float(limit), _ptr(_f32c(state)),
+                                       _ptr(_f32c(out)), int(bool(update_state)), _ptr(skip), _stream()),
+        "repo_return_scale_finish",
+    )
+    return out
+
+
+def scale_by(gmul, a, b=None, c=None):
+    """a *= gmul[0] in place, and b, c where given (same element count): include/repo_hip.h, repo_scale_by."""
+    n = a.numel()
+    assert gmul.numel() == 1 and all(t is None or t.numel() == n for t in (b, c))
+    check(
+        lib().repo_scale_by(n, _ptr(_f32c(a)), _ptr(_f32c(b)) if b is not None else None,
+                            _ptr(_f32c(c)) if c is not None else None, _ptr(_f32c(gmul)), _stream()),
+        "repo_scale_by",
+    )
 
 
 # ----------------------------------------------------------------------------- optimiser
