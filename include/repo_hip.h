@@ -677,6 +677,33 @@ int repo_tanh_normal_reinforce_gmul(int64_t rows, int64_t A, const float* mean, 
                                     uint64_t noise_seed, uint64_t noise_offset, const float* returns, const float* baseline,
                                     const float* weights, float gscale, const float* gmul, float* dmean, float* dstd,
                                     float* sums2, void* ws, size_t ws_bytes, hipStream_t stream);
+/* ABI v14, additions -- the two-hot symlog critic (config.value_dist = "twohot"; Hafner et al. 2023: the
+ * reference has no counterpart).  The value head writes K logits z per row over bins b_k = low + k delta, delta =
+ * (high - low) / (K - 1), uniform in symlog space; p = softmax(z), symlog(x) = sign(x) log1p(|x|), symexp its inverse.
+ * logits (rows, K) fp32 at row pitch ld >= K, dlogits likewise at ldd >= K (floats); nothing outside a row's K elements is
+ * read or written.  16-byte accesses where a base is 16-byte aligned and its pitch a multiple of 4, dwords otherwise: any
+ * ld >= K is accepted.  One wave per row, repo_twohot_geometry()'s rows_per_block rows per 256-thread block, at most
+ * max_blocks blocks (a grid-stride loop above that).
+ *   repo_twohot_decode:      m = sum_k p_k b_k, v_out[row] = symexp(m); m_out (nullable)[row] = m.
+ *   repo_twohot_decode_bwd:  dlogits[row][k] = g[row] * (gmul ? *gmul : 1) * (|v| + 1) p_k (b_k - m): the derivative of v.
+ *   repo_twohot_nll:         y = clamp(symlog(returns[row]), low, high), pos = (y - low) / delta, k0 = min(floor(pos), K - 2),
+ *                            t_{k0+1} = pos - k0, t_{k0} = 1 - t_{k0+1}, every other t_k = 0 (formed by comparison per lane,
+ *                            never by an indexed store); CE = -sum_k t_k log_softmax(z)_k; w = weights ? weights[row] : 1;
+ *                            sums2 = {sum w CE, sum w}; dlogits (nullable)[row][k] = scale w (p_k - t_k).  +-inf returns
+ *                            clamp to an end bin; a NaN return makes every element of its gradient row and sums2[0] NaN
+ *                            and addresses nothing.  A streaming reduction like repo_scalar_nll: `ws` is the reduction
+ *                            workspace (zeroed header), grids of at most last_block_max_grid blocks finish their own sum.
+ * rows <= 0, rows >= 2^31, K < 2, K > 1024, ld < K or (dlogits given) ldd < K: REPO_E_SHAPE; a NULL logits / v_out / g /
+ * dlogits (decode_bwd) / returns / sums2, non-finite bounds or !(low < high): REPO_E_BADARG; ws NULL or ws_bytes below
+ * repo_reduce_workspace_bytes(): REPO_E_WS_TOO_SMALL. */
+int repo_twohot_geometry(int* rows_per_block, int* last_block_max_grid, int* max_blocks);
+int repo_twohot_decode(int64_t rows, int64_t K, const float* logits, int64_t ld, float low, float high, float* v_out,
+                       float* m_out, hipStream_t stream);
+int repo_twohot_decode_bwd(int64_t rows, int64_t K, const float* logits, int64_t ld, float low, float high, const float* g,
+                           float* dlogits, int64_t ldd, const float* gmul, hipStream_t stream);
+int repo_twohot_nll(int64_t rows, int64_t K, const float* logits, int64_t ld, const float* returns, const float* weights,
+                    float low, float high, float scale, float* dlogits, int64_t ldd, float* sums2, void* ws,
+                    size_t ws_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------ inverse-dynamics auxiliary (ABI v10)
  * config.inv_dynamics: InverseDynamicsModel (models/utils.py:84-109) trained on DETACHED latents after every

@@ -29,7 +29,7 @@ from ... import functional as Fn
 from ... import ops
 from ...common.buffers import SequenceReplayBuffer
 from ...common.utils import get_device, postprocess, to_np
-from .models.actor_critic import ActorModel, ValueModel
+from .models.actor_critic import ActorModel, ValueModel, value_dist_config
 from .models.decoder import ContinuationModel, ObservationModel, RewardModel
 from .models.encoder import Encoder
 from .models.rssm import TransitionModel
@@ -212,6 +212,9 @@ class Dreamer:
     # config.return_norm = True (the returns term of the actor objective divided by the running percentile range of the
     # imagined returns): Dreamer and RePo.  The sibling families keep the raw returns: they refuse.
     _BUILDS_RETURN_NORM = True
+    # config.value_dist = "twohot" (the critic as a categorical over bins uniform in symlog space): Dreamer and
+    # RePo.  The sibling families keep the scalar head: they refuse anything but "normal".
+    _BUILDS_VALUE_DIST = True
 
     def build_models(self, config, env):
         self._conv_precision = getattr(config, "conv_precision", "highest")
@@ -263,6 +266,12 @@ class Dreamer:
             raise NotImplementedError(
                 f"return_norm=True: {type(self).__name__} weighs its actor objective in raw reward units; return "
                 "normalisation is built for Dreamer and RePo")
+        self._value_dist, self._value_bins, self._value_low, self._value_high = value_dist_config(config)
+        if self._value_dist != "normal" and not self._BUILDS_VALUE_DIST:
+            raise NotImplementedError(
+                f"value_dist={self._value_dist!r}: {type(self).__name__} regresses a scalar value head; the two-hot critic "
+                "is built for Dreamer and RePo")
+        self._twohot = self._value_dist == "twohot"
         obs_size = env.observation_space.shape
         action_size = int(np.prod(env.action_space.shape))
         self.action_size = action_size
@@ -310,8 +319,13 @@ class Dreamer:
             config.belief_size, config.state_size, config.hidden_size, action_size, config.dense_activation_function
         ).to(dev)
         self.value_model = ValueModel(
-            config.belief_size, config.state_size, config.hidden_size, config.dense_activation_function
+            config.belief_size, config.state_size, config.hidden_size, config.dense_activation_function,
+            **self._value_head_kw()
         ).to(dev)
+
+    def _value_head_kw(self):
+        """config.value_dist = "twohot": the value head's (and its slow target's) last layer has value_bins outputs."""
+        return {"bins": self._value_bins} if self._twohot else {}
 
     def _build_optimizers(self, config):
         dev = self.device
@@ -349,7 +363,8 @@ class Dreamer:
         opt = self.value_optimizer
         with torch.random.fork_rng(devices=[]):
             self.slow_value_model = ValueModel(
-                config.belief_size, config.state_size, config.hidden_size, config.dense_activation_function
+                config.belief_size, config.state_size, config.hidden_size, config.dense_activation_function,
+                **self._value_head_kw()
             ).to(self.device)
         self._slow_value_flat = opt.flat.clone()
         for q, o in zip(self.slow_value_model.plist(), opt.offsets):
@@ -732,7 +747,28 @@ class Dreamer:
         mix = self._actor_mix
         v_all = torch.empty((Hm + 1) * N, 1, device=dev) if mix < 1.0 else None
         vt_out = v_all[N:] if mix < 1.0 else None
-        if self._slow_value:
+        twohot = self._twohot
+        if twohot:
+            # config.value_dist = "twohot" (DESIGN.md 6o): the heads write K logits per row (at a pitch of a multiple of 4
+            # floats: the kernels' 16-byte path); one streaming launch decodes them into the (rows, 1) values everything
+            # below reads, straight into v_all where that exists.  zt: the logits behind the returns (the slow target's when
+            # there is one); z_on: the online head's on the rows its own loss reads.
+            K, b_lo, b_hi = self._value_bins, self._value_low, self._value_high
+            zt = ops.twohot_rows(Hm * N, K, dev)
+            if self._slow_value:
+                ps, _ = self._pg(self.slow_value_model)
+                _, vt_hid = ops.mlp_fwd(ps, feats, out=zt, act=act_v)
+                z_on = ops.twohot_rows(nv, K, dev)
+                _, v_hid = ops.mlp_fwd(pv, feats[:nv], out=z_on, act=act_v)
+            else:
+                _, v_hid = ops.mlp_fwd(pv, feats, out=zt, act=act_v)
+                vt_hid, z_on = v_hid, zt[:nv]
+            vt_pred = ops.twohot_decode(zt, b_lo, b_hi, out=vt_out)
+            if mix < 1.0:
+                z0 = ops.twohot_rows(N, K, dev)
+                ops.mlp_fwd(ps if self._slow_value else pv, x_all[:N], out=z0, act=act_v)
+                ops.twohot_decode(z0, b_lo, b_hi, out=v_all[:N])
+        elif self._slow_value:
             # the returns' values and bootstrap row come from the slow target on all Hm * N rows; the online head runs on
             # the rows its own loss reads
             ps, _ = self._pg(self.slow_value_model)
@@ -741,7 +777,7 @@ class Dreamer:
         else:
             v_pred, v_hid = ops.mlp_fwd(pv, feats, out=vt_out, act=act_v)
             vt_pred = v_pred
-        if mix < 1.0:
+        if mix < 1.0 and not twohot:
             ops.mlp_fwd(ps if self._slow_value else pv, x_all[:N], out=v_all[:N], act=act_v)
         # -- action entropy on the (attached) imagined states (dreamer.py:320-324).  The reference
         #    re-runs the actor on imag[0..Hm-1]; rows of steps 1..Hm-1 are the very inputs the rollout
@@ -820,9 +856,16 @@ class Dreamer:
         dfeat = torch.empty(Hm * N, Fw, device=dev) if dyn else torch.zeros(Hm * N, Fw, device=dev)
         main = torch.cuda.current_stream(dev)
         side = self._ac_side_stream or main
-        one_chain = dyn and not self._slow_value and os.environ.get("REPO_VALUE_ONE_CHAIN", "1") == "1"
+        #    With value_dist = "twohot" the gradient at the head's output is K wide and differs per loss (the decode's
+        #    reverse for the actor, p - t for the critic): the one-chain trick is the scalar head's, so two chains run, as
+        #    under slow_value_target, and REPO_VALUE_ONE_CHAIN is not read.
+        one_chain = (dyn and not self._slow_value and not twohot
+                     and os.environ.get("REPO_VALUE_ONE_CHAIN", "1") == "1")
         if dyn:
-            if self._slow_value:
+            if twohot:   # dv (return_norm's scalar already in it) -> (Hm * N, K) through the head the returns were built from
+                dzt = ops.twohot_decode_bwd(zt, b_lo, b_hi, dv.view(-1))
+                ops.mlp_bwd(ps if self._slow_value else pv, feats, vt_hid, dzt, dparams=None, dx=dfeat, act=act_v)
+            elif self._slow_value:
                 ops.mlp_bwd(ps, feats, vt_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
             elif one_chain:
                 v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), weights, 1.0 / ((Hm - 1) * gN))
@@ -838,7 +881,10 @@ class Dreamer:
         #    while the reverse rollout (which fills only ~77 CUs) and the actor backward proceed on the main stream
         side.wait_stream(main)  # after the value head's backward above read the weights
         with torch.cuda.stream(side):
-            if not one_chain:   # (slow target: v_pred and v_hid have the nv rows already)
+            if twohot:   # v_sums = [sum w CE, sum w]: the two slots of the scalar head's sums
+                v_sums, dz2 = ops.twohot_nll(z_on, returns.view(-1), weights, b_lo, b_hi, 1.0 / ((Hm - 1) * gN))
+                ops.mlp_bwd(pv, feats[:nv], [h[:nv] for h in v_hid], dz2, dparams=gv, dx=None, act=act_v)
+            elif not one_chain:   # (slow target: v_pred and v_hid have the nv rows already)
                 v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), weights, 1.0 / ((Hm - 1) * gN))
                 ops.mlp_bwd(pv, feats[:nv], [h[:nv] for h in v_hid], dv2.view(nv, 1), dparams=gv, dx=None, act=act_v)
             if self.dp is None:
@@ -986,7 +1032,9 @@ class Dreamer:
             out["train/return_scale"], out["train/return_lo"], out["train/return_hi"] = rn[0], rn[2], rn[3]
         out["train/actor_loss"] = (-ret / ((Hm - 1) * gN) - c.action_ent_coef * action_entropy
                                    - c.latent_ent_coef * latent_entropy)
-        if self._pcont:   # ret = sum w R, _vn = sum w: the weighted means over the (Hm - 1) * gN elements
+        if self._twohot:   # vsq = sum w CE: a cross-entropy, no Normal constant
+            out["train/value_loss"] = vsq / ((Hm - 1) * gN)
+        elif self._pcont:   # ret = sum w R, _vn = sum w: the weighted means over the (Hm - 1) * gN elements
             out["train/value_loss"] = (vsq + 0.5 * LOG_2PI * _vn) / ((Hm - 1) * gN)
         else:
             out["train/value_loss"] = vsq / ((Hm - 1) * gN) + 0.5 * LOG_2PI
@@ -1267,7 +1315,21 @@ class Dreamer:
             for k, v in own.items():
                 v.copy_(sd[k].to(v.device))
 
+    def _check_value_head(self, key, module, sd):
+        """A checkpoint written under the other value_dist (or another value_bins) has a last layer of another width: say
+        so, instead of _load_module's assert or a broadcast copy of a (1, hidden) weight into (K, hidden)."""
+        own = module.state_dict()
+        for k in ("fc4.weight", "fc4.bias"):
+            if k in sd and k in own and tuple(sd[k].shape) != tuple(own[k].shape):
+                raise ValueError(
+                    f"checkpoint {key}.{k} has shape {tuple(sd[k].shape)}, this agent's has {tuple(own[k].shape)}: it was "
+                    f"written with another value_dist / value_bins (this agent: value_dist={self._value_dist!r}"
+                    + (f", value_bins={self._value_bins}" if self._twohot else "") + ")")
+
     def load_param_dict(self, params):
+        self._check_value_head("value_model", self.value_model, params["value_model"])
+        if self._slow_value and "slow_value_model" in params:
+            self._check_value_head("slow_value_model", self.slow_value_model, params["slow_value_model"])
         self.step = params["step"]
         for name in ("encoder", "transition_model", "obs_model", "reward_model", "actor_model", "value_model"):
             self._load_module(getattr(self, name), params[name])

@@ -7,8 +7,53 @@ from .... import ops
 from .decoder import _ScalarHead
 
 
+VALUE_DISTS = ("normal", "twohot")
+
+
+def value_dist_config(config):
+    """config.value_dist and its three keys -> (name, bins, low, high).  value_dist: "normal" (the default:
+    the reference's scalar head under a unit-variance Normal) or "twohot" (K logits over bins uniform in symlog space);
+    value_bins (default 255) an integer in 2 .. 1024; value_bin_low / value_bin_high (-20.0 / 20.0) finite, low < high.  An
+    unknown name or a value outside its range raises ValueError, whichever head is asked for."""
+    import math
+    import numbers
+
+    name = getattr(config, "value_dist", "normal")
+    if name not in VALUE_DISTS:
+        raise ValueError(f'value_dist={name!r}: expected "normal" or "twohot"')
+    bins = getattr(config, "value_bins", 255)
+    if isinstance(bins, bool) or not isinstance(bins, numbers.Integral) or not 2 <= int(bins) <= 1024:
+        raise ValueError(f"value_bins={bins!r}: expected an integer in 2 .. 1024")
+    low, high = getattr(config, "value_bin_low", -20.0), getattr(config, "value_bin_high", 20.0)
+    for key, v in (("value_bin_low", low), ("value_bin_high", high)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(float(v)):
+            raise ValueError(f"{key}={v!r}: expected a finite number")
+    if not float(low) < float(high):
+        raise ValueError(f"value_bin_low={low!r}, value_bin_high={high!r}: expected low < high")
+    return name, int(bins), float(low), float(high)
+
+
 class ValueModel(_ScalarHead):
-    pass
+    """The scalar head (bins=None), or with config.value_dist = "twohot" the same trunk with `bins` logits in its last
+    layer.  That layer's weight and bias are zeroed behind the usual draw, as DreamerV3 does: the head starts at uniform
+    probabilities, a decoded value of exactly 0 for symmetric bins."""
+
+    def __init__(self, belief_size, state_size, hidden_size, activation_function="relu", bins=None):
+        super().__init__(belief_size, state_size, hidden_size, activation_function)
+        self.bins = bins
+        if bins is not None:
+            # the scalar layer above has drawn what it always draws; the wide one draws under a forked generator, so
+            # whatever is constructed behind this module initialises as it does with the scalar head
+            with torch.random.fork_rng(devices=[]):
+                self.fc4 = nn.Linear(hidden_size, int(bins))
+            with torch.no_grad():
+                self.fc4.weight.zero_()
+                self.fc4.bias.zero_()
+
+    def forward(self, belief, state):
+        if self.bins is not None:
+            raise NotImplementedError("the two-hot value head's logits are decoded by ops.twohot_decode (train_actor_critic)")
+        return super().forward(belief, state)
 
 
 class ActorModel(nn.Module):

@@ -137,6 +137,21 @@ __device__ __forceinline__ void last_block_finishes(const float* parts, int nval
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// The streaming reductions' launch shape (loss.hip, twohot.hip): one partial per workgroup, at most kRedBlocks of them.
+// reduction workspace: [zeroed header: the ticket word of last_block_finishes | partials].  A grid of at most
+// kLastBlockMaxGrid blocks finishes its own sum (ticket given); a larger one gets the follow-up launch (ticket null),
+// red_finish: loss.hip's final_sum_kernel, one block, the same order and arithmetic.
+constexpr int kRedBlocks = 1024;  // max partials per reduction
+inline int red_blocks(long n, int per_block) {
+  long b = (n + per_block - 1) / per_block;
+  if (b < 1) b = 1;
+  if (b > kRedBlocks) b = kRedBlocks;
+  return (int)b;
+}
+inline float* red_parts(void* ws) { return (float*)((char*)ws + kRedHeaderBytes); }
+inline unsigned* red_ticket(void* ws, int blocks) { return blocks <= kLastBlockMaxGrid ? (unsigned*)ws : nullptr; }
+int red_finish(void* ws, int blocks, int nvals, float* out, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------------- noise
 // Standard normals from a counter-based generator (Philox4x32-10, Salmon et al. SC'11; key = seed, counter =
 // element index / 4) + Box-Muller, so that a kernel can DRAW the reparameterisation noise it needs instead of

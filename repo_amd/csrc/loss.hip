@@ -8,8 +8,6 @@
 
 namespace repo {
 
-constexpr int kRedBlocks = 1024;  // max partials per reduction
-
 __global__ void final_sum_kernel(const float* __restrict__ parts, int n, int nvals, float* __restrict__ out) {
   // parts is [nvals][n]; out[v] = sum_i parts[v][i]
   __shared__ float red[16];
@@ -540,27 +538,18 @@ __global__ __launch_bounds__(256) void tia_blend_nll_kernel(int n4, int pix4, co
   last_block_finishes(parts, 8, red_out, ticket, red);
 }
 
-static inline int red_blocks(long n, int per_block) {
-  long b = (n + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > kRedBlocks) b = kRedBlocks;
-  return (int)b;
+// (red_blocks, red_parts, red_ticket: common.h -- csrc/twohot.hip's reduction shares them and this follow-up launch)
+int red_finish(void* ws, int blocks, int nvals, float* out, hipStream_t s) {
+  if (blocks <= kLastBlockMaxGrid) return REPO_OK;   // the launch's last block has written `out`
+  hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, red_parts(ws), blocks, nvals, out);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? REPO_OK : (int)e;
 }
 
 }  // namespace repo
 
 using namespace repo;
 
-// reduction workspace: [zeroed header: the ticket word of last_block_finishes | partials].  A grid of at most
-// kLastBlockMaxGrid blocks finishes its own sum (ticket given); a larger one gets the follow-up launch (ticket null).
-static inline float* red_parts(void* ws) { return (float*)((char*)ws + kRedHeaderBytes); }
-static inline unsigned* red_ticket(void* ws, int blocks) { return blocks <= kLastBlockMaxGrid ? (unsigned*)ws : nullptr; }
-static int red_finish(void* ws, int blocks, int nvals, float* out, hipStream_t s) {
-  if (blocks <= kLastBlockMaxGrid) return REPO_OK;   // the launch's last block has written `out`
-  hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, red_parts(ws), blocks, nvals, out);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? REPO_OK : (int)e;
-}
 extern "C" size_t repo_reduce_workspace_bytes(void) { return kRedHeaderBytes + 2 * kRedBlocks * sizeof(float); }
 
 extern "C" int repo_kl_balance(int64_t rows, int64_t S, const float* pm, const float* ps, const float* qm,

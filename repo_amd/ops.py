@@ -1193,6 +1193,81 @@ def scale_by(gmul, a, b=None, c=None):
     )
 
 
+# ----------------------------------------------------------------------------- two-hot symlog critic
+def twohot_geometry():
+    """(rows per block, largest grid that finishes its own sum, block cap) of the repo_twohot_* kernels: the row counts at
+    which their launch changes regime."""
+    r, g, b = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().repo_twohot_geometry(ctypes.addressof(r), ctypes.addressof(g), ctypes.addressof(b)), "repo_twohot_geometry")
+    return r.value, g.value, b.value
+
+
+def twohot_rows(rows, K, device):
+    """A (rows, K) fp32 view at a row pitch rounded up to 4 floats: the kernels' 16-byte path, and what the head's dense
+    chain reads and writes through its leading dimension."""
+    ld = (int(K) + 3) // 4 * 4
+    return torch.empty(rows, ld, dtype=torch.float32, device=device)[:, :K]
+
+
+def twohot_decode(logits, low, high, out=None, want_mean=False):
+    """logits (rows, K) with contiguous rows at any pitch -> v (rows, 1) = symexp(sum_k softmax(logits)_k b_k), written into
+    `out` (rows elements, contiguous) where given; want_mean: -> (v, m) with m (rows,) the mean in symlog space
+    (include/repo_hip.h, repo_twohot_decode)."""
+    rows, K = logits.shape
+    dev = logits.device
+    if out is None:
+        out = torch.empty(rows, 1, dtype=torch.float32, device=dev)
+    assert out.numel() == rows
+    m = torch.empty(rows, dtype=torch.float32, device=dev) if want_mean else None
+    check(
+        lib().repo_twohot_decode(rows, K, _ptr(logits), _ld(logits), float(low), float(high), _ptr(_f32c(out)), _ptr(m),
+                                 _stream()),
+        "repo_twohot_decode",
+    )
+    return (out, m) if want_mean else out
+
+
+def twohot_decode_bwd(logits, low, high, g, out=None, gmul=None):
+    """dlogits (rows, K) = g (|v| + 1) p (b - m), the derivative of twohot_decode's v times g (rows elements); gmul: a
+    one-element device tensor multiplied in, or None (include/repo_hip.h, repo_twohot_decode_bwd)."""
+    rows, K = logits.shape
+    assert g.numel() == rows and (gmul is None or gmul.numel() == 1)
+    if out is None:
+        out = twohot_rows(rows, K, logits.device)
+    assert out.shape == logits.shape
+    check(
+        lib().repo_twohot_decode_bwd(rows, K, _ptr(logits), _ld(logits), float(low), float(high), _ptr(_f32c(g)), _ptr(out),
+                                     _ld(out), _ptr(_f32c(gmul)) if gmul is not None else None, _stream()),
+        "repo_twohot_decode_bwd",
+    )
+    return out
+
+
+def twohot_nll(logits, returns, weights, low, high, scale, want_grad=True, out=None, dlogits=None):
+    """The two-hot cross-entropy of logits (rows, K) against returns (rows elements), weights (rows elements) or None for
+    ones (include/repo_hip.h, repo_twohot_nll) -> (sums2 = [sum w CE, sum w], dlogits (rows, K) = scale w (p - t) or
+    None)."""
+    rows, K = logits.shape
+    dev = logits.device
+    assert returns.numel() == rows and (weights is None or weights.numel() == rows)
+    if want_grad and dlogits is None:
+        dlogits = twohot_rows(rows, K, dev)
+    if not want_grad:
+        dlogits = None
+    assert dlogits is None or dlogits.shape == logits.shape
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = reduce_ws(dev)
+    check(
+        lib().repo_twohot_nll(rows, K, _ptr(logits), _ld(logits), _ptr(_f32c(returns)),
+                              _ptr(_f32c(weights)) if weights is not None else None, float(low), float(high), float(scale),
+                              _ptr(dlogits), _ld(dlogits) if dlogits is not None else 0, _ptr(out), _ptr(ws), ws.numel(),
+                              _stream()),
+        "repo_twohot_nll",
+    )
+    return out, dlogits
+
+
 # ----------------------------------------------------------------------------- optimiser
 def grad_sqnorm(g, out=None):
     if out is None:
