@@ -960,6 +960,51 @@ int repo_clip_adam_target(int64_t n, float* params, const float* grads, float* e
                           int64_t step, const unsigned* skip_if_nonzero, float* target, float fraction,
                           hipStream_t stream);
 
+/* Additions -- per-tensor adaptive gradient clipping and the LaProp update (config.grad_clip = "agc", config.optimizer =
+ * "laprop"; Brock et al. 2021, Ziyin et al. 2020, Hafner et al. 2023: the reference has no counterpart).
+ * repo_abi_version() stays 14: pure additions, repo_grad_sqnorm / repo_clip_adam / repo_clip_adam_target are untouched.
+ *
+ * The flat buffer of n floats holds nseg tensors, each at a 16-byte aligned offset and followed by 0..3 padding floats.
+ * Two DEVICE tables describe it, built once by the caller:
+ *   chunks:    nchunk x int[4] {offset, numel, segment, 0}, 16-byte aligned: each tensor cut into pieces of at most
+ *              `chunk` elements (repo_agc_geometry), in buffer order; only a tensor's last chunk may have numel % 4 != 0;
+ *   seg_first: nseg + 1 ints, segment s owns chunks [seg_first[s], seg_first[s + 1]).
+ * A table entry that points outside the buffer poisons its result with NaN (norms) or is not stepped; nothing is read or
+ * written out of bounds.
+ *
+ * repo_agc_coef (two launches whatever nseg is: agc_parts_kernel over min(nchunk, parts_max_blocks) blocks, then
+ * agc_finish_kernel, one block of finish_threads threads, a 64-lane wave per segment; no atomics, fixed summation order):
+ *   parts: 2 * nchunk floats of scratch (per chunk: sum g^2, sum p^2 over its numel elements, never the padding);
+ *   norms[2 s], norms[2 s + 1] = |g_s|^2, |p_s|^2;
+ *   coef[s] = |g_s| <= upper ? 1 : upper / |g_s| with upper = clip * max(pmin, |p_s|); a NaN norm gives a NaN coefficient;
+ *   stats[0] = sum_s |g_s|^2 (the pre-clip global squared gradient norm), stats[1] = the number of s with coef[s] < 1.
+ * n <= 0, n >= 2^31, nseg <= 0, nchunk < nseg, nchunk > n or nchunk > 2^30: REPO_E_SHAPE; a NULL pointer, or clip / pmin not finite and
+ * > 0: REPO_E_BADARG; params, grads or chunks not 16-byte aligned: REPO_E_ALIGN. */
+int repo_agc_geometry(int* chunk, int* parts_max_blocks, int* finish_threads, int* step_max_blocks);
+int repo_agc_coef(int64_t n, int64_t nseg, int64_t nchunk, const int* chunks, const int* seg_first, const float* params,
+                  const float* grads, float clip, float pmin, float* parts, float* norms, float* coef, float* stats,
+                  hipStream_t stream);
+/* The optimiser step in ONE launch (kernel optim_step_kernel<rule, clip_mode, target>), under repo_clip_adam's skip word:
+ *   g' = c g with c = 1 (REPO_CLIP_NONE), min(1, max_norm / (sqrt(*sqnorm) + 1e-6)) (REPO_CLIP_GLOBAL), or coef[segment]
+ *   (REPO_CLIP_TABLE: the chunk table is walked, the padding behind a tensor is stepped with that tensor's coefficient);
+ *   REPO_OPT_ADAM:   repo_clip_adam's expressions on g' (REPO_CLIP_NONE / _GLOBAL: its bits);
+ *   REPO_OPT_LAPROP: v = b2 v + (1 - b2) g'^2;  u = g' / (sqrt(v) / sqrt(1 - b2^step) + eps);
+ *                    m = b1 m + (1 - b1) u;  p -= lr / (1 - b1^step) * m;
+ *   target non-NULL: repo_clip_adam_target's mix of `target` towards the parameter just written, fraction in (0, 1].
+ * Grid: min(step_max_blocks, ceil(n / 256)) blocks, or min(step_max_blocks, nchunk) under REPO_CLIP_TABLE.
+ * n <= 0, step < 1, (table) n >= 2^31, nseg <= 0, nchunk < nseg, nchunk > n or nchunk > 2^30: REPO_E_SHAPE; a NULL buffer, an unknown rule
+ * or clip_mode, REPO_CLIP_GLOBAL without sqnorm, REPO_CLIP_TABLE without chunks / coef, a target with fraction outside
+ * (0, 1]: REPO_E_BADARG; chunks not 16-byte aligned: REPO_E_ALIGN. */
+#define REPO_OPT_ADAM 0
+#define REPO_OPT_LAPROP 1
+#define REPO_CLIP_NONE 0
+#define REPO_CLIP_GLOBAL 1
+#define REPO_CLIP_TABLE 2
+int repo_optim_step(int64_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int rule, int clip_mode,
+                    const float* sqnorm, float max_norm, int64_t nseg, int64_t nchunk, const int* chunks, const float* coef,
+                    float lr, float beta1, float beta2, float eps, int64_t step, const unsigned* skip_if_nonzero,
+                    float* target, float fraction, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,7 @@ from .models.actor_critic import ActorModel, ValueModel, value_dist_config
 from .models.decoder import ContinuationModel, ObservationModel, RewardModel
 from .models.encoder import Encoder
 from .models.rssm import TransitionModel
-from .models.utils import FlatAdam, InverseDynamicsModel
+from .models.utils import FlatAdam, InverseDynamicsModel, optim_config
 from .rollout import EpisodeDriver
 
 LOG_2PI = math.log(2.0 * math.pi)
@@ -174,7 +174,7 @@ class Dreamer:
         self._pending_pcont = None   # config.pcont: the continuation head's BCE sum of the last model step
         self._pending_rf = None      # config.actor_grad: the score-function term's two sums of the last actor-critic step
         self._pending_rn = None      # config.return_norm: [scale, 1 / scale, lo, hi] of the last actor-critic step
-        self._log_host = torch.empty(32, dtype=torch.float32).pin_memory()
+        self._log_host = torch.empty(48, dtype=torch.float32).pin_memory()
         self._act_graphs = {}
         self._act_graph_enabled = os.environ.get("REPO_ACT_GRAPH", "1") == "1"
         self._last_scalars = {}
@@ -215,6 +215,10 @@ class Dreamer:
     # config.value_dist = "twohot" (the critic as a categorical over bins uniform in symlog space): Dreamer and
     # RePo.  The sibling families keep the scalar head: they refuse anything but "normal".
     _BUILDS_VALUE_DIST = True
+    # config.grad_clip = "agc" / config.optimizer = "laprop" (per-tensor adaptive gradient clipping and the LaProp update in
+    # every FlatAdam the agent owns): Dreamer and RePo.  The sibling families keep the global-norm clip and
+    # Adam: they refuse any other value.
+    _BUILDS_OPTIM_RULES = True
 
     def build_models(self, config, env):
         self._conv_precision = getattr(config, "conv_precision", "highest")
@@ -272,6 +276,13 @@ class Dreamer:
                 f"value_dist={self._value_dist!r}: {type(self).__name__} regresses a scalar value head; the two-hot critic "
                 "is built for Dreamer and RePo")
         self._twohot = self._value_dist == "twohot"
+        self._optim_kw = optim_config(config)
+        self._agc = self._optim_kw["grad_clip"] == "agc"
+        if (self._agc or self._optim_kw["rule"] != "adam") and not self._BUILDS_OPTIM_RULES:
+            raise NotImplementedError(
+                f"grad_clip={self._optim_kw['grad_clip']!r}, optimizer={self._optim_kw['rule']!r}: {type(self).__name__} "
+                "steps with Adam behind the global-norm clip; adaptive gradient clipping and LaProp are built for Dreamer "
+                "and RePo")
         obs_size = env.observation_space.shape
         action_size = int(np.prod(env.action_space.shape))
         self.action_size = action_size
@@ -296,7 +307,8 @@ class Dreamer:
                 config.belief_size, config.state_size, action_size, config.inv_dynamics_hidden_size,
                 config.dense_activation_function,
             ).to(self.device)
-            self.inv_dynamics_optimizer = FlatAdam(self.inv_dynamics.parameters(), lr=config.inv_dynamics_lr)
+            self.inv_dynamics_optimizer = FlatAdam(self.inv_dynamics.parameters(), lr=config.inv_dynamics_lr,
+                                                   **self._optim_kw)
 
     def _build_modules(self, config, env, obs_size, action_size):
         """The six modules (the multitask agents build the task-conditioned ones instead: dreamer_mt.py)."""
@@ -337,14 +349,16 @@ class Dreamer:
         )
         if self._pcont:   # behind the reward head: the same bucket of a data-parallel job, the same clip norm
             self.model_params += list(self.pcont_model.parameters())
-        self.model_optimizer = FlatAdam(self.model_params, lr=config.model_lr)
+        self.model_optimizer = FlatAdam(self.model_params, lr=config.model_lr, **self._optim_kw)
         # the actor's and the critic's flat gradients are the two halves of ONE buffer: a data-parallel job
         # exchanges them as a single 1.18 MB bucket
         na = FlatAdam.padded_numel(list(self.actor_model.parameters()))
         nv = FlatAdam.padded_numel(list(self.value_model.parameters()))
         self._ac_grad = torch.zeros(na + nv, dtype=torch.float32, device=dev)
-        self.actor_optimizer = FlatAdam(self.actor_model.parameters(), lr=config.actor_lr, grad=self._ac_grad[:na])
-        self.value_optimizer = FlatAdam(self.value_model.parameters(), lr=config.value_lr, grad=self._ac_grad[na:])
+        self.actor_optimizer = FlatAdam(self.actor_model.parameters(), lr=config.actor_lr, grad=self._ac_grad[:na],
+                                        **self._optim_kw)
+        self.value_optimizer = FlatAdam(self.value_model.parameters(), lr=config.value_lr, grad=self._ac_grad[na:],
+                                        **self._optim_kw)
         # model gradient buckets of a data-parallel job, in the order the backward finishes them: [decoder +
         # reward head) is final when the decoder backward joins, [encoder + RSSM) after the encoder backward
         n_head = len(list(self.encoder.parameters())) + len(list(self.transition_model.parameters()))
@@ -952,6 +966,11 @@ class Dreamer:
             rns, self._pending_rn = self._pending_rn, None   # ride behind the extra gradient norms, which are not summed
             rns.record_stream(cur)
             xn = torch.cat([xn, rns])
+        if self._agc:   # config.grad_clip = "agc": each optimiser's clipped-tensor count, the last of the unsummed entries
+            opts = [self.model_optimizer, self.actor_optimizer, self.value_optimizer]
+            if self._inv_dyn:
+                opts.append(self.inv_dynamics_optimizer)
+            xn = torch.cat([xn] + [o.agc_count for o in opts])
         parts = [msc[:4], ret_sum, ent_sum, lat_sum, v_sums, xs, msc[4:5], self.actor_optimizer.sqnorm,
                  self.value_optimizer.sqnorm, xn]
         if dual is not None:
@@ -1001,6 +1020,10 @@ class Dreamer:
         xsums, h = h[9 : 9 + nxs], h[:9] + h[9 + nxs :]
         gm, ga_, gv_ = h[9:12]
         xnorms, h = h[12 : 12 + nxn], h[:12] + h[12 + nxn :]
+        agc = None
+        if self._agc:   # [.., clipped tensors of model, actor, value (, inv_dynamics)] (see _log_update)
+            k = 4 if self._inv_dyn else 3
+            xnorms, agc = xnorms[:-k], xnorms[-k:]
         rn = None
         if self._return_norm:   # [.., scale, 1 / scale, lo, hi] (see _log_update)
             xnorms, rn = xnorms[:-4], xnorms[-4:]
@@ -1040,6 +1063,9 @@ class Dreamer:
             out["train/value_loss"] = vsq / ((Hm - 1) * gN) + 0.5 * LOG_2PI
         out["train/action_entropy"] = action_entropy
         out["train/latent_entropy"] = latent_entropy
+        if agc is not None:
+            for name, count in zip(("model", "actor", "value", "inv_dynamics"), agc):
+                out[f"train/agc_clipped_{name}"] = count
         self._last_scalars = out
         self.last_grad_norms = {"model": math.sqrt(max(gm, 0.0)), "actor": math.sqrt(max(ga_, 0.0)),
                                 "value": math.sqrt(max(gv_, 0.0))}
@@ -1330,6 +1356,10 @@ class Dreamer:
         self._check_value_head("value_model", self.value_model, params["value_model"])
         if self._slow_value and "slow_value_model" in params:
             self._check_value_head("slow_value_model", self.slow_value_model, params["slow_value_model"])
+        # config.optimizer: every optimiser entry's rule is checked before anything -- a weight, the step
+        # count -- is taken from the checkpoint
+        for name in ("model", "actor", "value") + (("inv_dynamics",) if self._inv_dyn and "inv_dynamics" in params else ()):
+            getattr(self, f"{name}_optimizer").check_rule(params[f"{name}_optimizer"], f"the checkpoint's {name}_optimizer")
         self.step = params["step"]
         for name in ("encoder", "transition_model", "obs_model", "reward_model", "actor_model", "value_model"):
             self._load_module(getattr(self, name), params[name])

@@ -40,6 +40,7 @@ class MultitaskDreamer(Dreamer):
     _BUILDS_ACTOR_GRAD = False       # actor_grad="reinforce" / "both": built and tested for Dreamer and RePo
     _BUILDS_RETURN_NORM = False      # return_norm=True: built and tested for Dreamer and RePo
     _BUILDS_VALUE_DIST = False   # value_dist="twohot": built and tested for Dreamer and RePo
+    _BUILDS_OPTIM_RULES = False   # grad_clip="agc" / optimizer="laprop": built and tested for Dreamer and RePo
 
     def __init__(self, config, env, eval_env, logger):
         super().__init__(config, env, eval_env, logger)

@@ -9,6 +9,8 @@ global-norm clip and the Adam update are two streaming kernels over the flat buf
 data-parallel all-reduce is one collective.  state_dict()/load_state_dict() keep
 torch.optim.Adam's layout so reference checkpoints round-trip.
 """
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -61,21 +63,59 @@ def adam_param_group(lr, betas, eps, n_params):
     return group
 
 
+GRAD_CLIPS = ("norm", "agc")
+OPTIMIZERS = ("adam", "laprop")
+
+
+def _positive(config, key, default):
+    v = getattr(config, key, default)
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not v > 0:
+        raise ValueError(f"{key}={v!r}: expected a finite number > 0")
+    return float(v)
+
+
+def optim_config(config):
+    """config.grad_clip / config.optimizer and their keys -> the keyword arguments of FlatAdam that carry
+    them.  grad_clip: "norm" (the default: the global-norm clip at grad_clip_norm) or "agc" (per tensor, a gradient at
+    most agc_clip (0.3) times max(agc_pmin (1e-3), its tensor's norm); grad_clip_norm is then not applied).  optimizer:
+    "adam" (the default) or "laprop"; optimizer_eps, where present, replaces the rule's eps (1e-8 / 1e-20).  An unknown
+    name or an out-of-range number: ValueError naming the key."""
+    clip = getattr(config, "grad_clip", "norm")
+    if clip not in GRAD_CLIPS:
+        raise ValueError(f'grad_clip={clip!r}: expected "norm" or "agc"')
+    rule = getattr(config, "optimizer", "adam")
+    if rule not in OPTIMIZERS:
+        raise ValueError(f'optimizer={rule!r}: expected "adam" or "laprop"')
+    kw = {"rule": rule, "grad_clip": clip, "agc_clip": _positive(config, "agc_clip", 0.3),
+          "agc_pmin": _positive(config, "agc_pmin", 1e-3)}
+    kw["eps"] = _positive(config, "optimizer_eps", LAPROP_EPS if rule == "laprop" else 1e-8)
+    return kw
+
+
+LAPROP_EPS = 1e-20
+
+
 class FlatAdam:
-    """Adam over a flat parameter buffer with fused global-norm clipping."""
+    """Adam (or LaProp: rule="laprop") over a flat parameter buffer with fused global-norm clipping (or per-tensor adaptive
+    clipping: grad_clip="agc"), DESIGN.md 6p.  With the defaults every launch is the one it was before the two keys."""
 
     @staticmethod
     def padded_numel(params):
         """Length of the flat buffer FlatAdam lays these parameters out in (16-byte aligned sub-views)."""
         return sum((p.numel() + 3) // 4 * 4 for p in params)
 
-    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, grad=None):
-        """grad: optional caller-owned storage for the flat gradient (padded_numel floats) -- the agents
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=None, grad=None, rule="adam", grad_clip="norm", agc_clip=0.3,
+                 agc_pmin=1e-3):
+        """eps: None = the rule's default (1e-8, LaProp 1e-20).  grad: optional caller-owned storage for the flat gradient (padded_numel floats) -- the agents
         lay the actor's and the critic's gradients out in ONE buffer so that a data-parallel job exchanges
         them with one collective."""
         self.params = list(params)
         assert self.params, "FlatAdam needs at least one parameter"
+        assert rule in OPTIMIZERS and grad_clip in GRAD_CLIPS, (rule, grad_clip)
+        if eps is None:
+            eps = LAPROP_EPS if rule == "laprop" else 1e-8
         self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
+        self.rule, self.grad_clip, self.agc_clip, self.agc_pmin = rule, grad_clip, float(agc_clip), float(agc_pmin)
         self.step_count = 0
         dev = self.params[0].device
         sizes = [p.numel() for p in self.params]
@@ -93,6 +133,12 @@ class FlatAdam:
         self.exp_avg = torch.zeros(off, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=dev)
         self.sqnorm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.agc = None
+        if grad_clip == "agc":
+            # the tables, uploaded once; the pre-clip global squared norm lands in self.sqnorm, the clipped-tensor count
+            # behind it in self.agc_count
+            self.agc = ops.AgcTables(self.offsets, sizes, off, dev)
+            self.sqnorm, self.agc_count = self.agc.stats[:1], self.agc.stats[1:]
         self.skip = None   # the current update's status word (ops.take_scan_status): non-zero = the step is skipped
         self.target = None   # (flat, every, fraction) of a tracked slow copy: track_target
         self.gviews = []
@@ -111,7 +157,8 @@ class FlatAdam:
         (repo_adapt.py:29) -- two torch optimisers over shared parameters."""
         self = cls.__new__(cls)
         self.params = parent.params[:n_params]
-        self.lr, self.betas, self.eps = float(lr), parent.betas, parent.eps
+        self.lr, self.betas, self.eps = float(lr), parent.betas, (parent.eps if parent.rule == "adam" else 1e-8)
+        self.rule, self.grad_clip, self.agc = "adam", "norm", None   # a view stays Adam with the global clip
         self.step_count = 0
         self.offsets = parent.offsets[:n_params]
         self.numel = parent.offsets[n_params] if n_params < len(parent.params) else parent.numel
@@ -142,7 +189,13 @@ class FlatAdam:
 
     def _step(self, sqnorm, max_norm):
         target = self.target
-        if target is not None and self.step_count % target[1] == 0:
+        if self.rule != "adam" or self.agc is not None:
+            mix = target is not None and self.step_count % target[1] == 0
+            mode = ops.CLIP_TABLE if self.agc is not None else ops.CLIP_GLOBAL if sqnorm is not None else ops.CLIP_NONE
+            ops.optim_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.step_count, self.rule, mode,
+                           sqnorm, max_norm, self.agc, None, self.betas, self.eps, self.skip,
+                           target[0] if mix else None, target[2] if mix else 1.0)
+        elif target is not None and self.step_count % target[1] == 0:
             ops.clip_adam_target(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, sqnorm, max_norm, self.lr,
                                  self.step_count, target[0], target[2], self.betas, self.eps, skip=self.skip)
         else:
@@ -153,10 +206,15 @@ class FlatAdam:
         """clip_grad_norm_(params, max_norm) + step() (repo.py:89-90).  The squared global
         norm stays on the device in self.sqnorm (read it after the update's single sync)."""
         self.step_count += 1
-        ops.grad_sqnorm(self.grad, out=self.sqnorm)
+        if self.agc is not None:   # per tensor: max_norm is not applied
+            ops.agc_coef(self.agc, self.flat, self.grad, self.agc_clip, self.agc_pmin)
+        else:
+            ops.grad_sqnorm(self.grad, out=self.sqnorm)
         self._step(self.sqnorm, max_norm)
 
     def step(self):
+        """The unclipped step (the GAN discriminator's): no clipping of either kind."""
+        assert self.agc is None, "step() is the unclipped step; an AGC optimiser steps through clip_and_step"
         self.step_count += 1
         self._step(None, 0.0)
 
@@ -171,9 +229,22 @@ class FlatAdam:
                     "exp_avg": self.exp_avg[o : o + n].view(p.shape).clone(),
                     "exp_avg_sq": self.exp_avg_sq[o : o + n].view(p.shape).clone(),
                 }
-        return {"state": state, "param_groups": [adam_param_group(self.lr, self.betas, self.eps, len(self.params))]}
+        group = adam_param_group(self.lr, self.betas, self.eps, len(self.params))
+        if self.rule != "adam":   # the moments keep Adam's slots; one entry names the rule (Adam's layout is unchanged)
+            group["optimizer"] = self.rule
+        return {"state": state, "param_groups": [group]}
+
+    def check_rule(self, sd, what="the checkpoint's optimiser state"):
+        """ValueError naming `optimizer` if the state dict `sd` was written under the other update rule (the other rule's
+        first moment is another quantity).  Copies nothing: an agent calls it for every optimiser entry before it loads
+        anything (Dreamer.load_param_dict)."""
+        rule = sd["param_groups"][0].get("optimizer", "adam")
+        if rule != self.rule:
+            raise ValueError(f"optimizer={self.rule!r}: {what} was written under optimizer={rule!r}; the first moments "
+                             "of the two rules are not interchangeable")
 
     def load_state_dict(self, sd):
+        self.check_rule(sd)   # ahead of any copy
         g = sd["param_groups"][0]
         self.lr, self.betas, self.eps = float(g["lr"]), tuple(g["betas"]), float(g["eps"])
         steps = set()

@@ -48,6 +48,7 @@ class FinetunedRePo(RePo):
     _BUILDS_ACTOR_GRAD = False   # actor_grad="reinforce" / "both": built and tested for Dreamer and RePo
     _BUILDS_RETURN_NORM = False   # return_norm=True: built and tested for Dreamer and RePo
     _BUILDS_VALUE_DIST = False   # value_dist="twohot": built and tested for Dreamer and RePo
+    _BUILDS_OPTIM_RULES = False   # grad_clip="agc" / optimizer="laprop": built and tested for Dreamer and RePo
     _BUILDS_SYMBOLIC = False   # pixel_obs=False: train_encoder runs the conv encoder's passes (the reference pins uint8 frames)
     _BUILDS_CONV_PRECISION = False   # conv_precision="high": built and tested for Dreamer and RePo
 
@@ -165,6 +166,7 @@ class CalibratedRePo(RePo):
     _BUILDS_ACTOR_GRAD = False   # actor_grad="reinforce" / "both": built and tested for Dreamer and RePo
     _BUILDS_RETURN_NORM = False   # return_norm=True: built and tested for Dreamer and RePo
     _BUILDS_VALUE_DIST = False   # value_dist="twohot": built and tested for Dreamer and RePo
+    _BUILDS_OPTIM_RULES = False   # grad_clip="agc" / optimizer="laprop": built and tested for Dreamer and RePo
     _BUILDS_SYMBOLIC = False   # pixel_obs=False: the calibration frames are paired pixel frames (uint8, 6 channels)
     _BUILDS_CONV_PRECISION = False   # conv_precision="high": built and tested for Dreamer and RePo
     _LOG_KEYS = ("f_loss_src", "f_loss_tgt", "f_kl", "aln_loss", "calib_loss", "encoder_loss")

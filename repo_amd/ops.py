@@ -1301,6 +1301,86 @@ def clip_adam_target(p, g, m, v, sqnorm, max_norm, lr, step, target, fraction, b
     )
 
 
+# per-tensor adaptive clipping and LaProp
+OPT_RULES = {"adam": 0, "laprop": 1}                   # REPO_OPT_*
+CLIP_NONE, CLIP_GLOBAL, CLIP_TABLE = 0, 1, 2           # REPO_CLIP_*
+
+
+def agc_geometry():
+    """(chunk elements, the norm pass's block cap, the finishing block's threads, the step's block cap) of repo_agc_coef /
+    repo_optim_step: the sizes at which their launches change regime."""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    check(lib().repo_agc_geometry(*(ctypes.addressof(x) for x in v)), "repo_agc_geometry")
+    return tuple(x.value for x in v)
+
+
+class AgcTables:
+    """The segment and chunk tables of a flat buffer (include/repo_hip.h, repo_agc_coef), built and uploaded once, with the
+    outputs that go with them.  offsets / sizes: each tensor's start (a multiple of 4) and element count, in buffer order;
+    n: the buffer's length.  `out` holds [norms (2 nseg) | coef (nseg) | stats (2)] in one allocation: norms, coef and
+    stats are views of it."""
+
+    def __init__(self, offsets, sizes, n, device):
+        chunk = agc_geometry()[0]
+        rows, first = [], [0]
+        for s, (o, k) in enumerate(zip(offsets, sizes)):
+            o, k = int(o), int(k)
+            assert k > 0 and o % 4 == 0 and 0 <= o and o + k <= n, (o, k, n)
+            for c in range(0, k, chunk):
+                rows.append((o + c, min(chunk, k - c), s, 0))
+            first.append(len(rows))
+        self.n, self.nseg, self.nchunk = int(n), len(sizes), len(rows)
+        self.chunks = torch.tensor(rows, dtype=torch.int32).to(device)
+        self.seg_first = torch.tensor(first, dtype=torch.int32).to(device)
+        self.parts = torch.zeros(2 * self.nchunk, dtype=torch.float32, device=device)
+        self.out = torch.zeros(3 * self.nseg + 2, dtype=torch.float32, device=device)
+        self.norms = self.out[: 2 * self.nseg]
+        self.coef = self.out[2 * self.nseg : 3 * self.nseg]
+        self.stats = self.out[3 * self.nseg :]
+
+
+def agc_coef(tables, p, g, clip, pmin, norms=None, coef=None, stats=None):
+    """Per-tensor squared norms, clipping coefficients and [global squared gradient norm, clipped count] of the flat
+    buffers p / g under `tables` (two launches, nothing read back) -> (norms, coef, stats), tables' own unless given."""
+    t = tables
+    assert p.numel() == t.n and g.numel() == t.n
+    norms = t.norms if norms is None else norms
+    coef = t.coef if coef is None else coef
+    stats = t.stats if stats is None else stats
+    assert norms.numel() == 2 * t.nseg and coef.numel() == t.nseg and stats.numel() == 2
+    check(
+        lib().repo_agc_coef(t.n, t.nseg, t.nchunk, _ptr(t.chunks), _ptr(t.seg_first), _ptr(_f32c(p)), _ptr(_f32c(g)),
+                            float(clip), float(pmin), _ptr(t.parts), _ptr(_f32c(norms)), _ptr(_f32c(coef)),
+                            _ptr(_f32c(stats)), _stream()),
+        "repo_agc_coef",
+    )
+    return norms, coef, stats
+
+
+def optim_step(p, g, m, v, lr, step, rule="adam", clip_mode=CLIP_NONE, sqnorm=None, max_norm=0.0, tables=None, coef=None,
+               betas=(0.9, 0.999), eps=1e-8, skip=None, target=None, fraction=1.0):
+    """The one-launch optimiser step (include/repo_hip.h, repo_optim_step): rule "adam" / "laprop"; clip_mode CLIP_NONE,
+    CLIP_GLOBAL (sqnorm, max_norm: clip_adam's coefficient) or CLIP_TABLE (tables, coef: one coefficient per tensor);
+    target / fraction: clip_adam_target's mix in the same launch; skip: the update's status word."""
+    t = tables
+    n = p.numel()
+    assert g.numel() == n and m.numel() == n and v.numel() == n, (n, g.numel(), m.numel(), v.numel())
+    assert sqnorm is None or sqnorm.numel() == 1
+    if clip_mode == CLIP_TABLE:
+        assert t is not None and t.n == n, "CLIP_TABLE steps a buffer of its tables' length"
+        assert (t.coef if coef is None else coef).numel() == t.nseg
+    if target is not None:
+        assert target.numel() == n and target.dtype == torch.float32 and target.is_contiguous()
+    check(
+        lib().repo_optim_step(p.numel(), _ptr(_f32c(p)), _ptr(_f32c(g)), _ptr(_f32c(m)), _ptr(_f32c(v)), OPT_RULES[rule],
+                              int(clip_mode), _ptr(sqnorm), float(max_norm), t.nseg if t is not None else 0,
+                              t.nchunk if t is not None else 0, _ptr(t.chunks) if t is not None else None,
+                              _ptr(coef if coef is not None or t is None else t.coef), float(lr), betas[0], betas[1],
+                              float(eps), step, _ptr(skip), _ptr(target), float(fraction), _stream()),
+        "repo_optim_step",
+    )
+
+
 def philox_normal(n, seed, offset, device):
     """The n standard normals [offset, offset+n) of Philox stream `seed` -- what a kernel given (seed, offset)
     instead of a noise tensor draws for elements 0..n-1."""
