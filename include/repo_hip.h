@@ -1005,6 +1005,33 @@ int repo_optim_step(int64_t n, float* params, const float* grads, float* exp_avg
                     float lr, float beta1, float beta2, float eps, int64_t step, const unsigned* skip_if_nonzero,
                     float* target, float fraction, hipStream_t stream);
 
+/* Additions -- the world-model losses of DreamerV3 (config.obs_symlog, config.kl_dyn_scale / kl_rep_scale, DESIGN.md 6q;
+ * Hafner et al. 2023: the reference has no counterpart).  repo_abi_version() stays 14: pure additions, repo_kl_balance is
+ * untouched (its modes 0 and 1 run the expressions they ran, the same bits).
+ *
+ * repo_symlog: y[i] = copysign(log1p(|x[i]|), x[i]) for i < n (csrc/symlog.hip).  Odd in bits -- the magnitude depends on
+ * |x| alone and the sign bit is copied: symlog(-x) == -symlog(x), -0.0 -> -0.0; NaN -> NaN, +-inf -> +-inf; |x| < 2^-24
+ * (denormals included) returns x itself, which is log1p's correctly rounded value there.  y == x (in place) is allowed,
+ * any other overlap is not.  Nothing outside the n elements is read or written.  16-byte accesses where x and y are both
+ * 16-byte aligned and n >= vec_floats, then the n % vec_floats tail as dwords; dwords throughout otherwise.  `threads`
+ * threads per block, min(max_blocks, ceil(items / threads)) blocks with items = n / vec_floats (vector form) or n, a
+ * grid-stride loop above the cap (repo_symlog_geometry).  n == 0: nothing is launched, REPO_OK; n < 0: REPO_E_SHAPE;
+ * a NULL x or y (whatever n is): REPO_E_BADARG. */
+int repo_symlog_geometry(int* threads, int* vec_floats, int* max_blocks);
+int repo_symlog(int64_t n, const float* x, float* y, hipStream_t stream);
+/* repo_kl_balance_scaled: kl_kernel's mode 2, per row with free_nats as the per-row free bits.  The loss is
+ *   dyn * max(KL(sg q || p), free_nats) + rep * max(KL(q || sg p), free_nats)           (sg = stop gradient)
+ * per row, times `scale`.  *kl_sum = sum_rows max(KL_row, free_nats): repo_kl_balance mode 1's value, the same bits.
+ * With g = 1 where KL_row > free_nats, 0.5 at equality, 0 below (mode 1's tie rule):
+ *   dpm, dps = (prior-side derivative of KL_row)     * g * sp,   sp = dyn * scale,
+ *   dqm, dqs = (posterior-side derivative of KL_row) * g * sq,   sq = rep * scale,
+ * sp and sq each ONE fp32 product formed on the host, so that dpm / dps equal in bits mode 1's at scale = sp and dqm / dqs
+ * mode 1's at scale = sq; dyn = rep = 1 is mode 1 in every output.  Gradient outputs are nullable one by one.  Launch shape,
+ * workspace and shape errors: repo_kl_balance's.  dyn or rep negative or not finite: REPO_E_BADARG. */
+int repo_kl_balance_scaled(int64_t rows, int64_t S, const float* pm, const float* ps, const float* qm, const float* qs,
+                           float dyn, float rep, float free_nats, float scale, float* dpm, float* dps, float* dqm,
+                           float* dqs, float* kl_sum, void* ws, size_t ws_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

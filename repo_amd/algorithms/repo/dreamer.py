@@ -30,7 +30,7 @@ from ... import ops
 from ...common.buffers import SequenceReplayBuffer
 from ...common.utils import get_device, postprocess, to_np
 from .models.actor_critic import ActorModel, ValueModel, value_dist_config
-from .models.decoder import ContinuationModel, ObservationModel, RewardModel
+from .models.decoder import ContinuationModel, ObservationModel, RewardModel, reward_dist_config
 from .models.encoder import Encoder
 from .models.rssm import TransitionModel
 from .models.utils import FlatAdam, InverseDynamicsModel, optim_config
@@ -95,6 +95,36 @@ def return_norm_config(config):
     if not (limit > 0.0 and math.isfinite(limit)):
         raise ValueError(f"return_norm_limit={limit!r}: expected a finite float > 0")
     return bool(on), decay, low, high, limit
+
+
+def obs_symlog_config(config):
+    """config.obs_symlog -> bool: the state-vector encoder reads symlog(obs) and the decoder's loss is taken
+    against symlog(obs).  Anything but True / False raises ValueError, and so does True with pixel_obs=True: images are
+    not symlog-ed."""
+    on = getattr(config, "obs_symlog", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"obs_symlog={on!r}: expected True or False")
+    if on and config.pixel_obs:
+        raise ValueError("obs_symlog=True with pixel_obs=True: images are not symlog-ed; the key is for state-vector "
+                         "observations (pixel_obs=False)")
+    return bool(on)
+
+
+def kl_scales_config(config):
+    """config.kl_dyn_scale / config.kl_rep_scale -> (on, dyn, rep).  Both absent: (False, 1.0, 1.0), the V1
+    max(KL, free_nats) with equal weight on both sides.  Either present: the other defaults to DreamerV3's value (dyn 0.5,
+    rep 0.1).  A value that is not a finite number >= 0 raises ValueError."""
+    on = hasattr(config, "kl_dyn_scale") or hasattr(config, "kl_rep_scale")
+    if not on:
+        return False, 1.0, 1.0
+    out = []
+    for key, default in (("kl_dyn_scale", 0.5), ("kl_rep_scale", 0.1)):
+        v = getattr(config, key, default)
+        if (isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not math.isfinite(float(v))
+                or float(v) < 0.0):
+            raise ValueError(f"{key}={v!r}: expected a finite float >= 0")
+        out.append(float(v))
+    return True, out[0], out[1]
 
 
 def in_conv_precision(method):
@@ -219,6 +249,15 @@ class Dreamer:
     # every FlatAdam the agent owns): Dreamer and RePo.  The sibling families keep the global-norm clip and
     # Adam: they refuse any other value.
     _BUILDS_OPTIM_RULES = True
+    # config.reward_dist = "twohot" (the reward head as a categorical over bins uniform in symlog space): Dreamer
+    # and RePo.  The sibling families keep the scalar head: they refuse anything but "normal".
+    _BUILDS_REWARD_DIST = True
+    # config.obs_symlog = True (state vectors pass through symlog on their way to the encoder and as the decoder's target,
+    # DESIGN.md 6q): Dreamer and RePo with pixel_obs=False.  The sibling families read raw observations: they refuse.
+    _BUILDS_OBS_SYMLOG = True
+    # config.kl_dyn_scale / kl_rep_scale (the KL weighted per side, free bits on both): Dreamer.  RePo's KL is its
+    # own Lagrangian (kl_kernel mode 0) and every other family keeps its own: they refuse the keys.
+    _BUILDS_KL_SCALES = True
 
     def build_models(self, config, env):
         self._conv_precision = getattr(config, "conv_precision", "highest")
@@ -283,6 +322,22 @@ class Dreamer:
                 f"grad_clip={self._optim_kw['grad_clip']!r}, optimizer={self._optim_kw['rule']!r}: {type(self).__name__} "
                 "steps with Adam behind the global-norm clip; adaptive gradient clipping and LaProp are built for Dreamer "
                 "and RePo")
+        self._reward_dist, self._reward_bins, self._reward_low, self._reward_high = reward_dist_config(config)
+        if self._reward_dist != "normal" and not self._BUILDS_REWARD_DIST:
+            raise NotImplementedError(
+                f"reward_dist={self._reward_dist!r}: {type(self).__name__} regresses a scalar reward head; the two-hot "
+                "reward head is built for Dreamer and RePo")
+        self._rew_twohot = self._reward_dist == "twohot"
+        if getattr(config, "obs_symlog", False) is not False and not self._BUILDS_OBS_SYMLOG:   # (ahead of the pixel check)
+            raise NotImplementedError(
+                f"obs_symlog={config.obs_symlog!r}: {type(self).__name__} reads raw observations; symlog observations are "
+                "built for Dreamer and RePo on state vectors")
+        self._obs_symlog = obs_symlog_config(config)
+        self._kl_scaled, self._kl_dyn, self._kl_rep = kl_scales_config(config)
+        if self._kl_scaled and not self._BUILDS_KL_SCALES:
+            raise NotImplementedError(
+                f"kl_dyn_scale / kl_rep_scale: {type(self).__name__} weighs its KL term its own way (RePo: the Lagrangian of "
+                "its constraint); the two scales are built for Dreamer")
         obs_size = env.observation_space.shape
         action_size = int(np.prod(env.action_space.shape))
         self.action_size = action_size
@@ -324,7 +379,8 @@ class Dreamer:
             config.cnn_activation_function,
         ).to(dev)
         self.reward_model = RewardModel(
-            config.belief_size, config.state_size, config.hidden_size, config.dense_activation_function
+            config.belief_size, config.state_size, config.hidden_size, config.dense_activation_function,
+            **({"bins": self._reward_bins} if self._rew_twohot else {})
         ).to(dev)
         # quirk kept: dense_activation_function lands in ActorModel's `dist` slot (dreamer.py:99-105)
         self.actor_model = ActorModel(
@@ -476,6 +532,8 @@ class Dreamer:
         st = {"T": T, "B": B, "rows": rows, "grow": grow}
         # frame 0's embedding is never used (embeds[1:], repo.py:41): encode frames 1..L-1 only
         frames = obs[1:].reshape(rows, *obs.shape[2:])
+        if self._obs_symlog:   # one launch per batch: the buffer is the encoder's input AND the decoder's target (6q)
+            frames = ops.symlog(frames)
         st["frames"] = frames
         pe, _ = self._pg(self.encoder)
         if self._symbolic:
@@ -505,14 +563,29 @@ class Dreamer:
         else:
             st["nll_sum"], st["dec_saved"] = Fn.decoder_fwd_nll(pd, feat, frames, 1.0 / grow, head=head)
         # reward head; predicted from the next state, masked by nonterminal (repo.py:58-61)
-        pw, _ = self._pg(self.reward_model)
-        r_pred, st["rew_hid"] = ops.mlp_fwd(pw, feat, act=self.reward_model.act)
-        st["rew_sums"], st["drew"] = ops.scalar_nll(
-            r_pred.view(-1), rewards[:-1].reshape(-1).contiguous(), nonterms[:-1].reshape(-1).contiguous(), 1.0 / grow
-        )
+        st["rew_hid"], st["rew_sums"], st["drew"] = self._reward_forward(feat, rewards, nonterms, grow)
         if self._pcont:
             st["pc_hid"], st["dpc"] = self._pcont_forward(feat, nonterms, grow)
         return st
+
+    def _reward_forward(self, feat, rewards, nonterms, grow):
+        """The reward head's half of the model loss on the T*B feature rows, masked by nonterminal, the mean over ALL rows
+        (repo.py:58-61).  -> (hidden activations, [loss sum, mask sum], the gradient at the head's output).  "normal": the
+        scalar under a unit-variance Normal, gradient (rows, 1).  "twohot" (DESIGN.md 6q): K logits through the general MLP
+        path, the two-hot cross-entropy of symlog(reward) with the mask as its weights, gradient (rows, K); the two sums
+        keep the scalar head's two slots."""
+        pw, _ = self._pg(self.reward_model)
+        if self._rew_twohot:
+            z = ops.twohot_rows(feat.shape[0], self._reward_bins, feat.device)
+            _, hid = ops.mlp_fwd(pw, feat, out=z, act=self.reward_model.act)
+            sums, dz = ops.twohot_nll(z, rewards[:-1].reshape(-1).contiguous(), nonterms[:-1].reshape(-1).contiguous(),
+                                      self._reward_low, self._reward_high, 1.0 / grow)
+            return hid, sums, dz
+        r_pred, hid = ops.mlp_fwd(pw, feat, act=self.reward_model.act)
+        sums, drew = ops.scalar_nll(
+            r_pred.view(-1), rewards[:-1].reshape(-1).contiguous(), nonterms[:-1].reshape(-1).contiguous(), 1.0 / grow
+        )
+        return hid, sums, drew.view(-1, 1)
 
     def _pcont_forward(self, feat, nonterms, grow):
         """The continuation head's half of the model loss: logits on the T*B feature rows, BCE against the
@@ -539,7 +612,7 @@ class Dreamer:
         wside = self._wgrad_side(st["frames"].shape[0] // sv.featx[1:].shape[0])   # sequences in the batch
         dfeat = torch.empty(rows, feat.shape[1], device=dev)
         pw, gw = self._pg(self.reward_model)
-        ops.mlp_bwd(pw, feat, st["rew_hid"], st["drew"].view(rows, 1), dparams=gw, dx=dfeat, act=self.reward_model.act)
+        ops.mlp_bwd(pw, feat, st["rew_hid"], st["drew"], dparams=gw, dx=dfeat, act=self.reward_model.act)
         if self._pcont:
             self._pcont_backward(feat, st["pc_hid"], st["dpc"], dfeat)
         pd, gd = self._pg(self.obs_model)
@@ -654,8 +727,12 @@ class Dreamer:
         sv, grow = st["sv"], st["grow"]
         if sv.prior_ready is not None:
             torch.cuda.current_stream(self.device).wait_stream(sv.prior_ready)
-        kl_sum, kl_grads = ops.kl_balance(sv.prior_mean, sv.prior_std, sv.post_mean, sv.post_std, 1, 0.0, None,
-                                          float(c.free_nats), 1.0 / grow)
+        if self._kl_scaled:   # config.kl_dyn_scale / kl_rep_scale: mode 1's sum, the two sides weighted apart
+            kl_sum, kl_grads = ops.kl_balance(sv.prior_mean, sv.prior_std, sv.post_mean, sv.post_std, 2, self._kl_dyn, None,
+                                              float(c.free_nats), 1.0 / grow, rep=self._kl_rep)
+        else:
+            kl_sum, kl_grads = ops.kl_balance(sv.prior_mean, sv.prior_std, sv.post_mean, sv.post_std, 1, 0.0, None,
+                                              float(c.free_nats), 1.0 / grow)
         self._world_model_backward(st, kl_grads, decoder_attached=True)
         self._model_step()
         self._pending_model = (torch.cat([st["nll_sum"], st["rew_sums"], kl_sum, self.model_optimizer.sqnorm]), None,
@@ -748,7 +825,12 @@ class Dreamer:
         # reference computes it all the same): the head runs on the first Hm - 1 steps' rows, forward and backward
         nr_ = (Hm - 1) * N
         r_pred = torch.empty(Hm * N, 1, device=dev)
-        _, r_hid = ops.mlp_fwd(pw, feats[:nr_], out=r_pred[:nr_], act=act_w)
+        if self._rew_twohot:   # config.reward_dist = "twohot" (DESIGN.md 6q): K logits per row, one launch decodes them
+            zr = ops.twohot_rows(nr_, self._reward_bins, dev)
+            _, r_hid = ops.mlp_fwd(pw, feats[:nr_], out=zr, act=act_w)
+            ops.twohot_decode(zr, self._reward_low, self._reward_high, out=r_pred[:nr_])
+        else:
+            _, r_hid = ops.mlp_fwd(pw, feats[:nr_], out=r_pred[:nr_], act=act_w)
         if self._pcont:   # the continuation logits of the same rows (frozen head): p[t] = sigmoid, formed in the returns' kernel
             pc, _ = self._pg(self.pcont_model)
             c_logit = torch.empty(Hm * N, 1, device=dev)
@@ -886,8 +968,12 @@ class Dreamer:
                 ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=gv, dx=dfeat, dout_w=dv2.view(nv, 1), act=act_v)
             else:
                 ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
-            ops.mlp_bwd(pw, feats[:nr_], r_hid, dr.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_], accumulate_dx=True,
-                        act=act_w)
+            if self._rew_twohot:   # dr (return_norm's scalar already in it) -> (nr_, K) through the decode's reverse
+                dzr = ops.twohot_decode_bwd(zr, self._reward_low, self._reward_high, dr.view(-1)[:nr_])
+                ops.mlp_bwd(pw, feats[:nr_], r_hid, dzr, dparams=None, dx=dfeat[:nr_], accumulate_dx=True, act=act_w)
+            else:
+                ops.mlp_bwd(pw, feats[:nr_], r_hid, dr.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_],
+                            accumulate_dx=True, act=act_w)
             if self._pcont:   # through p inside the returns into the imagined states; the head's weights take nothing
                 ops.mlp_bwd(pc, feats[:nr_], c_hid, dc.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_],
                             accumulate_dx=True, act=self.pcont_model.act)
@@ -1030,12 +1116,19 @@ class Dreamer:
         npix = self._npix
         out = {}
         out["train/obs_loss"] = nll / grow + 0.5 * LOG_2PI * npix
-        out["train/reward_loss"] = (rsq + 0.5 * LOG_2PI * rmask) / grow
+        if self._rew_twohot:   # rsq = sum w CE: a cross-entropy, no Normal constant
+            out["train/reward_loss"] = rsq / grow
+        else:
+            out["train/reward_loss"] = (rsq + 0.5 * LOG_2PI * rmask) / grow
         if n_dual:
             self._dual_scalars(out, h[12 : 12 + n_dual])
         else:
             out["train/kl_loss"] = kl / grow
-        out["train/model_loss"] = out["train/obs_loss"] + out["train/reward_loss"] + out["train/kl_loss"]
+        if self._kl_scaled:   # kl_loss stays the sum of max(KL, free_nats) over rows; the loss weighs it per side
+            out["train/model_loss"] = (out["train/obs_loss"] + out["train/reward_loss"]
+                                       + (self._kl_dyn + self._kl_rep) * out["train/kl_loss"])
+        else:
+            out["train/model_loss"] = out["train/obs_loss"] + out["train/reward_loss"] + out["train/kl_loss"]
         rf = None
         if self._actor_mix < 1.0:   # [.., sum w adv logp, sum logp] (see _log_update)
             xsums, rf = xsums[:-2], xsums[-2:]
@@ -1189,6 +1282,8 @@ class Dreamer:
 
     @torch.no_grad()
     def _act_eager(self, belief, posterior_state, action, obs, explore):
+        if self._obs_symlog:   # (inside the captured region of the acting graph)
+            obs = ops.symlog(obs.contiguous())
         embed = self.encoder(obs)
         outs = self.transition_model.observe(belief, posterior_state, action.unsqueeze(0), embed.unsqueeze(0))
         belief, posterior_state = outs[0].squeeze(0), outs[4].squeeze(0)
@@ -1352,8 +1447,19 @@ class Dreamer:
                     f"written with another value_dist / value_bins (this agent: value_dist={self._value_dist!r}"
                     + (f", value_bins={self._value_bins}" if self._twohot else "") + ")")
 
+    def _check_reward_head(self, sd):
+        """The same for a reward_model written under the other reward_dist (or another reward_bins)."""
+        own = self.reward_model.state_dict()
+        for k in ("fc4.weight", "fc4.bias"):
+            if k in sd and k in own and tuple(sd[k].shape) != tuple(own[k].shape):
+                raise ValueError(
+                    f"checkpoint reward_model.{k} has shape {tuple(sd[k].shape)}, this agent's has {tuple(own[k].shape)}: it "
+                    f"was written with another reward_dist / reward_bins (this agent: reward_dist={self._reward_dist!r}"
+                    + (f", reward_bins={self._reward_bins}" if self._rew_twohot else "") + ")")
+
     def load_param_dict(self, params):
         self._check_value_head("value_model", self.value_model, params["value_model"])
+        self._check_reward_head(params["reward_model"])
         if self._slow_value and "slow_value_model" in params:
             self._check_value_head("slow_value_model", self.slow_value_model, params["slow_value_model"])
         # config.optimizer (DESIGN.md 6p): every optimiser entry's rule is checked before anything -- a weight, the step

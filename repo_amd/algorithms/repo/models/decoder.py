@@ -122,8 +122,55 @@ class _ScalarHead(nn.Module):
         return mlp_apply(self, belief, state).squeeze(dim=1)
 
 
+REWARD_DISTS = ("normal", "twohot")
+
+
+def reward_dist_config(config):
+    """config.reward_dist and its three keys -> (name, bins, low, high), value_dist_config's rules
+    (models/actor_critic.py) under the reward head's names.  reward_dist: "normal" (the default: the reference's scalar head
+    under a unit-variance Normal) or "twohot" (K logits over bins uniform in symlog space); reward_bins (default 255) an
+    integer in 2 .. 1024; reward_bin_low / reward_bin_high (-20.0 / 20.0) finite, low < high.  An unknown name or a value
+    outside its range raises ValueError, whichever head is asked for."""
+    import math
+    import numbers
+
+    name = getattr(config, "reward_dist", "normal")
+    if name not in REWARD_DISTS:
+        raise ValueError(f'reward_dist={name!r}: expected "normal" or "twohot"')
+    bins = getattr(config, "reward_bins", 255)
+    if isinstance(bins, bool) or not isinstance(bins, numbers.Integral) or not 2 <= int(bins) <= 1024:
+        raise ValueError(f"reward_bins={bins!r}: expected an integer in 2 .. 1024")
+    low, high = getattr(config, "reward_bin_low", -20.0), getattr(config, "reward_bin_high", 20.0)
+    for key, v in (("reward_bin_low", low), ("reward_bin_high", high)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(float(v)):
+            raise ValueError(f"{key}={v!r}: expected a finite number")
+    if not float(low) < float(high):
+        raise ValueError(f"reward_bin_low={low!r}, reward_bin_high={high!r}: expected low < high")
+    return name, int(bins), float(low), float(high)
+
+
 class RewardModel(_ScalarHead):
-    pass
+    """The scalar head (bins=None), or with config.reward_dist = "twohot" the same trunk with `bins` logits in its last
+    layer, built as ValueModel(bins=...) builds its own (models/actor_critic.py): the scalar layer draws what it always
+    draws, the wide one draws under a forked generator and is zeroed, so everything constructed behind this module
+    initialises as with "normal" and a fresh head decodes to exactly 0."""
+
+    def __init__(self, belief_size, state_size, hidden_size, activation_function="relu", bins=None):
+        super().__init__(belief_size, state_size, hidden_size, activation_function)
+        self.bins = bins
+        if bins is not None:
+            import torch
+
+            with torch.random.fork_rng(devices=[]):
+                self.fc4 = nn.Linear(hidden_size, int(bins))
+            with torch.no_grad():
+                self.fc4.weight.zero_()
+                self.fc4.bias.zero_()
+
+    def forward(self, belief, state):
+        if self.bins is not None:
+            raise NotImplementedError("the two-hot reward head's logits are decoded by ops.twohot_decode (train_actor_critic)")
+        return super().forward(belief, state)
 
 
 class ContinuationModel(_ScalarHead):

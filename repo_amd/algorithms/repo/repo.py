@@ -45,6 +45,10 @@ class _ScalarAdam:
 
 
 class RePo(Dreamer):
+    # config.kl_dyn_scale / kl_rep_scale: RePo's KL is the Lagrangian of its constraint with its own split
+    # (alpha, kl_kernel mode 0), not max(KL, free_nats): the keys are refused
+    _BUILDS_KL_SCALES = False
+
     def build_models(self, config, env):
         super().build_models(config, env)
         # scalar dual variable, kept as a 0-dim tensor like the reference (repo.py:17-22)
@@ -80,9 +84,7 @@ class RePo(Dreamer):
             act=self.transition_model.act)
         feat = sv.featx[1:].reshape(rows, D + S)
         pw, gw = self._pg(self.reward_model)
-        r_pred, r_hid = ops.mlp_fwd(pw, feat, act=self.reward_model.act)
-        rew_sums, drew = ops.scalar_nll(r_pred.view(-1), rewards[:-1].reshape(-1).contiguous(),
-                                        nonterms[:-1].reshape(-1).contiguous(), 1.0 / grow)
+        r_hid, rew_sums, drew = self._reward_forward(feat, rewards, nonterms, grow)   # (rows, 1), or (rows, K) two-hot
         if self._pcont:
             pc_hid, dpc = self._pcont_forward(feat, nonterms, grow)
         alpha = c.prior_train_steps / (1 + c.prior_train_steps)
@@ -92,7 +94,7 @@ class RePo(Dreamer):
         side.wait_stream(main)
         with torch.cuda.stream(side):
             dfeat = torch.empty(rows, D + S, device=dev)
-            ops.mlp_bwd(pw, feat, r_hid, drew.view(rows, 1), dparams=gw, dx=dfeat, act=self.reward_model.act)
+            ops.mlp_bwd(pw, feat, r_hid, drew, dparams=gw, dx=dfeat, act=self.reward_model.act)
             if self._pcont:
                 self._pcont_backward(feat, pc_hid, dpc, dfeat)
             ev_rew = torch.cuda.Event()

@@ -49,6 +49,9 @@ class FinetunedRePo(RePo):
     _BUILDS_RETURN_NORM = False   # return_norm=True: built and tested for Dreamer and RePo
     _BUILDS_VALUE_DIST = False   # value_dist="twohot": built and tested for Dreamer and RePo
     _BUILDS_OPTIM_RULES = False   # grad_clip="agc" / optimizer="laprop": built and tested for Dreamer and RePo
+    _BUILDS_REWARD_DIST = False   # reward_dist="twohot": built and tested for Dreamer and RePo
+    _BUILDS_OBS_SYMLOG = False   # obs_symlog=True: built and tested for Dreamer and RePo on state vectors
+    _BUILDS_KL_SCALES = False   # kl_dyn_scale / kl_rep_scale: built and tested for Dreamer
     _BUILDS_SYMBOLIC = False   # pixel_obs=False: train_encoder runs the conv encoder's passes (the reference pins uint8 frames)
     _BUILDS_CONV_PRECISION = False   # conv_precision="high": built and tested for Dreamer and RePo
 
@@ -167,6 +170,9 @@ class CalibratedRePo(RePo):
     _BUILDS_RETURN_NORM = False   # return_norm=True: built and tested for Dreamer and RePo
     _BUILDS_VALUE_DIST = False   # value_dist="twohot": built and tested for Dreamer and RePo
     _BUILDS_OPTIM_RULES = False   # grad_clip="agc" / optimizer="laprop": built and tested for Dreamer and RePo
+    _BUILDS_REWARD_DIST = False   # reward_dist="twohot": built and tested for Dreamer and RePo
+    _BUILDS_OBS_SYMLOG = False   # obs_symlog=True: built and tested for Dreamer and RePo on state vectors
+    _BUILDS_KL_SCALES = False   # kl_dyn_scale / kl_rep_scale: built and tested for Dreamer
     _BUILDS_SYMBOLIC = False   # pixel_obs=False: the calibration frames are paired pixel frames (uint8, 6 channels)
     _BUILDS_CONV_PRECISION = False   # conv_precision="high": built and tested for Dreamer and RePo
     _LOG_KEYS = ("f_loss_src", "f_loss_tgt", "f_kl", "aln_loss", "calib_loss", "encoder_loss")

@@ -55,6 +55,9 @@ class TIA(Dreamer):
     _BUILDS_RETURN_NORM = False      # return_norm=True: built and tested for Dreamer and RePo
     _BUILDS_VALUE_DIST = False   # value_dist="twohot": built and tested for Dreamer and RePo
     _BUILDS_OPTIM_RULES = False   # grad_clip="agc" / optimizer="laprop": built and tested for Dreamer and RePo
+    _BUILDS_REWARD_DIST = False   # reward_dist="twohot": built and tested for Dreamer and RePo
+    _BUILDS_OBS_SYMLOG = False   # obs_symlog=True: built and tested for Dreamer and RePo on state vectors
+    _BUILDS_KL_SCALES = False   # kl_dyn_scale / kl_rep_scale: built and tested for Dreamer
 
     # ------------------------------------------------------------------ construction
     def build_models(self, config, env):

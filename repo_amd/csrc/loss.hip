@@ -24,6 +24,9 @@ __global__ void final_sum_kernel(const float* __restrict__ parts, int n, int nva
 //   beta * (alpha * KL(sg q || p) + (1-alpha) * KL(q || sg p)) * scale
 // mode 1 (Dreamer, dreamer.py:278-282): out = sum_rows max(KL_row, free_nats); gradients of
 //   max(KL_row, free_nats) * scale on both sides (half of them for a row whose KL equals free_nats).
+// mode 2 (config.kl_dyn_scale / kl_rep_scale): mode 1's sum and tie rule; gradients of
+//   (dyn * max(KL(sg q || p), free_nats) + rep * max(KL(q || sg p), free_nats)) * scale -- the prior side weighted by
+//   dyn * scale, the posterior side by rep * scale, each ONE fp32 product formed by the host (repo_kl_balance_scaled).
 // One wave per row (S <= 64 lanes active).
 __global__ __launch_bounds__(256) void kl_kernel(int rows, int S, const float* __restrict__ pm,
                                                  const float* __restrict__ ps, const float* __restrict__ qm,
@@ -60,7 +63,10 @@ __global__ __launch_bounds__(256) void kl_kernel(int rows, int S, const float* _
     } else {
       // torch.max(kl, free_nats) is torch.maximum: at a tie each side receives half the gradient
       const bool active = klrow > free_nats;
-      wp = wq = active ? scale : klrow == free_nats ? 0.5f * scale : 0.f;
+      // mode 2: the host has formed the two sides' scales, `alpha` = dyn * scale and `scale` = rep * scale
+      const float sp = mode == 2 ? alpha : scale;
+      wp = active ? sp : klrow == free_nats ? 0.5f * sp : 0.f;
+      wq = active ? scale : klrow == free_nats ? 0.5f * scale : 0.f;
       if (lane == 0) acc += active ? klrow : free_nats;
     }
     if (lane < S) {
@@ -563,6 +569,24 @@ extern "C" int repo_kl_balance(int64_t rows, int64_t S, const float* pm, const f
   const int blocks = red_blocks(rows, 40);   // <= 64 blocks up to 2560 rows: the launch finishes its own sum (common.h)
   hipLaunchKernelGGL(kl_kernel, dim3(blocks), dim3(256), 0, stream, (int)rows, (int)S, pm, ps, qm, qs, mode, alpha,
                      log_beta, free_nats, scale, dpm, dps, dqm, dqs, red_parts(ws), kl_sum, red_ticket(ws, blocks));
+  REPO_CHECK_LAUNCH();
+  return red_finish(ws, blocks, 1, kl_sum, stream);
+}
+
+extern "C" int repo_kl_balance_scaled(int64_t rows, int64_t S, const float* pm, const float* ps, const float* qm,
+                                      const float* qs, float dyn, float rep, float free_nats, float scale, float* dpm,
+                                      float* dps, float* dqm, float* dqs, float* kl_sum, void* ws, size_t ws_bytes,
+                                      hipStream_t stream) {
+  REPO_ARCH_GUARD();
+  REPO_REQUIRE(rows > 0 && S > 0 && S <= 64 && rows * S < kMaxIdx, REPO_E_SHAPE);
+  REPO_REQUIRE(pm && ps && qm && qs && kl_sum && dyn >= 0.f && rep >= 0.f && dyn <= 3.4e38f && rep <= 3.4e38f,
+               REPO_E_BADARG);   // (a NaN scale fails both comparisons)
+  REPO_REQUIRE(ws && ws_bytes >= repo_reduce_workspace_bytes(), REPO_E_WS_TOO_SMALL);
+  const float sp = dyn * scale, sq = rep * scale;   // one fp32 product each
+  const int blocks = red_blocks(rows, 40);          // repo_kl_balance's launch shape
+  hipLaunchKernelGGL(kl_kernel, dim3(blocks), dim3(256), 0, stream, (int)rows, (int)S, pm, ps, qm, qs, 2, sp,
+                     (const float*)nullptr, free_nats, sq, dpm, dps, dqm, dqs, red_parts(ws), kl_sum,
+                     red_ticket(ws, blocks));
   REPO_CHECK_LAUNCH();
   return red_finish(ws, blocks, 1, kl_sum, stream);
 }

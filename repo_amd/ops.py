@@ -817,13 +817,26 @@ def rssm_imagine_bwd(rssm_params, sv, dfeat, dprior_mean=None, dprior_std=None, 
 
 
 # ----------------------------------------------------------------------------- losses
-def kl_balance(pm, ps, qm, qs, mode, alpha, log_beta, free_nats, scale, want_grads=True):
+def kl_balance(pm, ps, qm, qs, mode, alpha, log_beta, free_nats, scale, want_grads=True, rep=None):
+    """mode 0 / 1: repo_kl_balance.  mode 2 (config.kl_dyn_scale / kl_rep_scale): `alpha` carries the prior
+    side's weight dyn, `rep` the posterior side's (repo_kl_balance_scaled); log_beta is not read.  want_grads: True, False,
+    or four booleans (dpm, dps, dqm, dqs): the outputs left out are passed as NULL and returned as None."""
     S = pm.shape[-1]
     rows = pm.numel() // S
     dev = pm.device
-    g = [torch.empty_like(pm) for _ in range(4)] if want_grads else [None] * 4
+    want = [bool(want_grads)] * 4 if isinstance(want_grads, bool) else [bool(w) for w in want_grads]
+    g = [torch.empty_like(pm) if w else None for w in want]
     out = torch.empty(1, dtype=torch.float32, device=dev)
     ws = reduce_ws(dev)
+    if mode == 2:
+        assert rep is not None, "mode 2 takes the posterior side's weight in `rep`"
+        check(
+            lib().repo_kl_balance_scaled(rows, S, _ptr(_f32c(pm)), _ptr(_f32c(ps)), _ptr(_f32c(qm)), _ptr(_f32c(qs)),
+                                         float(alpha), float(rep), float(free_nats), float(scale), _ptr(g[0]), _ptr(g[1]),
+                                         _ptr(g[2]), _ptr(g[3]), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+            "repo_kl_balance_scaled",
+        )
+        return out, g
     check(
         lib().repo_kl_balance(rows, S, _ptr(_f32c(pm)), _ptr(_f32c(ps)), _ptr(_f32c(qm)), _ptr(_f32c(qs)), mode,
                               float(alpha), _ptr(log_beta), float(free_nats), float(scale), _ptr(g[0]), _ptr(g[1]),
@@ -1266,6 +1279,27 @@ def twohot_nll(logits, returns, weights, low, high, scale, want_grad=True, out=N
         "repo_twohot_nll",
     )
     return out, dlogits
+
+
+# ----------------------------------------------------------------------------- symlog observations
+def symlog_geometry():
+    """(threads per block, floats per 16-byte access, block cap) of repo_symlog: the element counts at which its launch
+    changes regime."""
+    t, v, b = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().repo_symlog_geometry(ctypes.addressof(t), ctypes.addressof(v), ctypes.addressof(b)), "repo_symlog_geometry")
+    return t.value, v.value, b.value
+
+
+def symlog(x, out=None):
+    """sign(x) log1p(|x|) of a contiguous fp32 tensor of any shape (include/repo_hip.h, repo_symlog) -> `out` (the same
+    element count, contiguous; `out is x`: in place), a fresh tensor of x's shape by default."""
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.numel() == x.numel()
+    if x.numel() == 0:   # (an empty tensor has no base address to hand over)
+        return out
+    check(lib().repo_symlog(x.numel(), _ptr(_f32c(x)), _ptr(_f32c(out)), _stream()), "repo_symlog")
+    return out
 
 
 # ----------------------------------------------------------------------------- optimiser
