@@ -704,6 +704,35 @@ int repo_twohot_decode_bwd(int64_t rows, int64_t K, const float* logits, int64_t
 int repo_twohot_nll(int64_t rows, int64_t K, const float* logits, int64_t ld, const float* returns, const float* weights,
                     float low, float high, float scale, float* dlogits, int64_t ldd, float* sums2, void* ws,
                     size_t ws_bytes, hipStream_t stream);
+/* ABI v14, additions -- the bin space and the paired cross-entropy of the two-hot heads (config.value_bin_space /
+ * reward_bin_space / value_slow_reg; Hafner et al. 2023, revised).  repo_abi_version() stays 14: pure
+ * additions, the three entry points above keep their signatures and their bits.  Sibling entry points of those three:
+ * the same geometry, alignment rules and error codes; `space` is 0 (symlog) or 1 (symexp), anything else REPO_E_BADARG.
+ *   space 0: the math of the three entry points above.  With target_b NULL the results equal theirs in bits.
+ *   space 1: the bins stand at B_k = symexp(b_k), b_k as above (for low == -high, B_{K-1-k} == -B_k in bits); bounds whose
+ *            symexp is not finite in fp32: REPO_E_BADARG.
+ *     repo_twohot_decode_x:      v_out[row] = sum_k p_k B_k, summed in symmetric pairs (p_{K-1-j} B_{K-1-j} + p_j B_j), the
+ *                                middle bin of an odd K alone, then across the pairs: equal logits over symmetric bins decode
+ *                                to exactly 0.0.  m_out (nullable)[row] = v.
+ *     repo_twohot_decode_bwd_x:  dlogits[row][k] = g[row] * (gmul ? *gmul : 1) * p_k (B_k - v).
+ *     repo_twohot_nll_x:         y = clamp(target, B_0, B_{K-1}) on the RAW target; k0 from symlog(y) on the uniform grid,
+ *                                moved by at most one bin so that B_{k0} <= y <= B_{k0+1}, k0 <= K - 2;
+ *                                t_{k0+1} = (y - B_{k0}) / (B_{k0+1} - B_{k0}) clamped to [0, 1], t_{k0} = 1 - t_{k0+1}.
+ *   both spaces, repo_twohot_nll_x: target_b (nullable) is a second target of the same rows with its own two-hot t_b; the
+ *     row's logsumexp is formed once; sums3 = {sum w CE_a, sum w, sum w CE_b} (sums3[2] = 0 without target_b) and
+ *     dlogits[row][k] = scale w ((p_k - t_a_k) + reg (p_k - t_b_k)) = scale w ((1 + reg) p_k - t_a_k - reg t_b_k).  reg is
+ *     ignored without target_b; with reg == 0 and finite t_b, dlogits and sums3[0:2] equal the unpaired call's in bits.  A
+ *     NaN target_a poisons its gradient row and sums3[0], a NaN target_b its gradient row and sums3[2]; neither addresses
+ *     anything.  `ws` holds three partials per block: ws_bytes below repo_twohot_nll_x_workspace_bytes() (or ws NULL):
+ *     REPO_E_WS_TOO_SMALL; a NULL target_a / sums3 or a non-finite or negative reg: REPO_E_BADARG. */
+size_t repo_twohot_nll_x_workspace_bytes(void);
+int repo_twohot_decode_x(int64_t rows, int64_t K, const float* logits, int64_t ld, float low, float high, int space,
+                         float* v_out, float* m_out, hipStream_t stream);
+int repo_twohot_decode_bwd_x(int64_t rows, int64_t K, const float* logits, int64_t ld, float low, float high, int space,
+                             const float* g, float* dlogits, int64_t ldd, const float* gmul, hipStream_t stream);
+int repo_twohot_nll_x(int64_t rows, int64_t K, const float* logits, int64_t ld, const float* target_a,
+                      const float* target_b, float reg, const float* weights, float low, float high, int space, float scale,
+                      float* dlogits, int64_t ldd, float* sums3, void* ws, size_t ws_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------ inverse-dynamics auxiliary (ABI v10)
  * config.inv_dynamics: InverseDynamicsModel (models/utils.py:84-109) trained on DETACHED latents after every

@@ -127,6 +127,45 @@ def kl_scales_config(config):
     return True, out[0], out[1]
 
 
+BIN_SPACES = ("symlog", "symexp")
+
+
+def twohot_space_config(config, family="Dreamer", builds_reg=True, builds_space=True):
+    """config.value_slow_reg, config.value_bin_space, config.reward_bin_space -> (reg, value space, reward
+    space).  value_slow_reg: a finite float >= 0, absent or 0 = off, the weight of the cross-entropy that pulls the critic
+    towards its slow copy's decoded prediction; it needs value_dist="twohot".  *_bin_space: "symlog" (the default: bins
+    uniform in symlog space, the decoded value symexp(sum p b)) or "symexp" (bins at symexp(b), the decoded value the
+    expectation sum p B); "symexp" needs the matching *_dist="twohot".  A value outside its range raises ValueError; a key
+    that is on in a family that does not build it (builds_reg / builds_space False) raises NotImplementedError naming it,
+    ahead of the checks against the other keys."""
+    reg = getattr(config, "value_slow_reg", 0.0)
+    if (isinstance(reg, (bool, np.bool_)) or not isinstance(reg, (int, float, np.floating, np.integer))
+            or not math.isfinite(float(reg)) or float(reg) < 0.0):
+        raise ValueError(f"value_slow_reg={reg!r}: expected a finite float >= 0")
+    reg = float(reg)
+    spaces = {}
+    for key in ("value_bin_space", "reward_bin_space"):
+        spaces[key] = getattr(config, key, "symlog")
+        if not isinstance(spaces[key], str) or spaces[key] not in BIN_SPACES:
+            raise ValueError(f'{key}={spaces[key]!r}: expected "symlog" or "symexp"')
+    if reg > 0.0 and not builds_reg:
+        raise NotImplementedError(
+            f"value_slow_reg={reg!r}: {family} regresses a scalar value head with no slow copy; the slow-critic "
+            "regulariser is built for Dreamer and RePo")
+    for key, v in spaces.items():
+        if v != "symlog" and not builds_space:
+            raise NotImplementedError(
+                f"{key}={v!r}: {family} has no two-hot head; symexp-spaced bins are built for Dreamer and RePo")
+    if reg > 0.0 and getattr(config, "value_dist", "normal") != "twohot":
+        raise ValueError(f"value_slow_reg={reg!r} with value_dist={getattr(config, 'value_dist', 'normal')!r}: the "
+                         'regulariser is a cross-entropy over the bins and needs value_dist="twohot"')
+    for key, dist in (("value_bin_space", "value_dist"), ("reward_bin_space", "reward_dist")):
+        if spaces[key] == "symexp" and getattr(config, dist, "normal") != "twohot":
+            raise ValueError(f'{key}="symexp" with {dist}={getattr(config, dist, "normal")!r}: there are no bins to place; '
+                             f'the key needs {dist}="twohot"')
+    return reg, spaces["value_bin_space"], spaces["reward_bin_space"]
+
+
 def in_conv_precision(method):
     """The agent method runs at the agent's convolution precision (config.conv_precision, ops.conv_precision): every path that
     launches conv kernels -- train_dynamics, the acting step with its graph capture, _reconstruct -- goes through this one
@@ -204,6 +243,7 @@ class Dreamer:
         self._pending_pcont = None   # config.pcont: the continuation head's BCE sum of the last model step
         self._pending_rf = None      # config.actor_grad: the score-function term's two sums of the last actor-critic step
         self._pending_rn = None      # config.return_norm: [scale, 1 / scale, lo, hi] of the last actor-critic step
+        self._pending_vreg = None    # config.value_slow_reg: the regulariser's sum w CE_b of the last actor-critic step
         self._log_host = torch.empty(48, dtype=torch.float32).pin_memory()
         self._act_graphs = {}
         self._act_graph_enabled = os.environ.get("REPO_ACT_GRAPH", "1") == "1"
@@ -258,6 +298,12 @@ class Dreamer:
     # config.kl_dyn_scale / kl_rep_scale (the KL weighted per side, free bits on both): Dreamer.  RePo's KL is its
     # own Lagrangian (kl_kernel mode 0) and every other family keeps its own: they refuse the keys.
     _BUILDS_KL_SCALES = True
+    # config.value_slow_reg (a second cross-entropy pulls the two-hot critic towards its slow copy's prediction, DESIGN.md
+    # 6r): Dreamer and RePo.  The sibling families have neither the two-hot critic nor a slow copy: they refuse.
+    _BUILDS_VALUE_SLOW_REG = True
+    # config.value_bin_space / reward_bin_space = "symexp" (the two-hot bins at symexp(b_k)): Dreamer and
+    # RePo.  The sibling families keep their scalar heads: they refuse anything but "symlog".
+    _BUILDS_BIN_SPACE = True
 
     def build_models(self, config, env):
         self._conv_precision = getattr(config, "conv_precision", "highest")
@@ -328,6 +374,10 @@ class Dreamer:
                 f"reward_dist={self._reward_dist!r}: {type(self).__name__} regresses a scalar reward head; the two-hot "
                 "reward head is built for Dreamer and RePo")
         self._rew_twohot = self._reward_dist == "twohot"
+        self._value_reg, self._value_space, self._reward_space = twohot_space_config(
+            config, type(self).__name__, self._BUILDS_VALUE_SLOW_REG, self._BUILDS_BIN_SPACE)
+        # a slow copy of the value head exists for the returns (6l), for the regulariser (6r), or for both
+        self._slow_copy = self._slow_value or self._value_reg > 0.0
         if getattr(config, "obs_symlog", False) is not False and not self._BUILDS_OBS_SYMLOG:   # (ahead of the pixel check)
             raise NotImplementedError(
                 f"obs_symlog={config.obs_symlog!r}: {type(self).__name__} reads raw observations; symlog observations are "
@@ -352,7 +402,7 @@ class Dreamer:
                 config.belief_size, config.state_size, config.hidden_size, config.dense_activation_function
             ).to(self.device)
         self._build_optimizers(config)
-        if self._slow_value:
+        if self._slow_copy:   # (the returns read it only under slow_value_target; value_slow_reg alone builds it too)
             self._build_slow_value(config)
         if self._return_norm:
             self._build_return_norm()
@@ -425,7 +475,7 @@ class Dreamer:
         self._dp_two_buckets = os.environ.get("REPO_DP_BUCKETS", "2") != "1"
 
     def _build_slow_value(self, config):
-        """config.slow_value_target: a second ValueModel whose parameters are views into ONE flat buffer with
+        """config.slow_value_target or config.value_slow_reg > 0 (6r): a second ValueModel whose parameters are views into ONE flat buffer with
         value_optimizer.flat's layout (same offsets, same padded length), a bit copy of the online head.  Built under a
         forked generator: it draws nothing from torch's stream, so everything constructed behind it initialises as it
         does with the key off.  Never in an optimiser, never takes a gradient; the value optimiser mixes it in the
@@ -579,8 +629,8 @@ class Dreamer:
             z = ops.twohot_rows(feat.shape[0], self._reward_bins, feat.device)
             _, hid = ops.mlp_fwd(pw, feat, out=z, act=self.reward_model.act)
             sums, dz = ops.twohot_nll(z, rewards[:-1].reshape(-1).contiguous(), nonterms[:-1].reshape(-1).contiguous(),
-                                      self._reward_low, self._reward_high, 1.0 / grow)
-            return hid, sums, dz
+                                      self._reward_low, self._reward_high, 1.0 / grow, space=self._reward_space)
+            return hid, sums[:2], dz   # ("symexp": the launch writes a third, unused sum)
         r_pred, hid = ops.mlp_fwd(pw, feat, act=self.reward_model.act)
         sums, drew = ops.scalar_nll(
             r_pred.view(-1), rewards[:-1].reshape(-1).contiguous(), nonterms[:-1].reshape(-1).contiguous(), 1.0 / grow
@@ -828,7 +878,7 @@ class Dreamer:
         if self._rew_twohot:   # config.reward_dist = "twohot" (DESIGN.md 6q): K logits per row, one launch decodes them
             zr = ops.twohot_rows(nr_, self._reward_bins, dev)
             _, r_hid = ops.mlp_fwd(pw, feats[:nr_], out=zr, act=act_w)
-            ops.twohot_decode(zr, self._reward_low, self._reward_high, out=r_pred[:nr_])
+            ops.twohot_decode(zr, self._reward_low, self._reward_high, out=r_pred[:nr_], space=self._reward_space)
         else:
             _, r_hid = ops.mlp_fwd(pw, feats[:nr_], out=r_pred[:nr_], act=act_w)
         if self._pcont:   # the continuation logits of the same rows (frozen head): p[t] = sigmoid, formed in the returns' kernel
@@ -849,7 +899,7 @@ class Dreamer:
             # floats: the kernels' 16-byte path); one streaming launch decodes them into the (rows, 1) values everything
             # below reads, straight into v_all where that exists.  zt: the logits behind the returns (the slow target's when
             # there is one); z_on: the online head's on the rows its own loss reads.
-            K, b_lo, b_hi = self._value_bins, self._value_low, self._value_high
+            K, b_lo, b_hi, v_space = self._value_bins, self._value_low, self._value_high, self._value_space
             zt = ops.twohot_rows(Hm * N, K, dev)
             if self._slow_value:
                 ps, _ = self._pg(self.slow_value_model)
@@ -859,11 +909,11 @@ class Dreamer:
             else:
                 _, v_hid = ops.mlp_fwd(pv, feats, out=zt, act=act_v)
                 vt_hid, z_on = v_hid, zt[:nv]
-            vt_pred = ops.twohot_decode(zt, b_lo, b_hi, out=vt_out)
+            vt_pred = ops.twohot_decode(zt, b_lo, b_hi, out=vt_out, space=v_space)
             if mix < 1.0:
                 z0 = ops.twohot_rows(N, K, dev)
                 ops.mlp_fwd(ps if self._slow_value else pv, x_all[:N], out=z0, act=act_v)
-                ops.twohot_decode(z0, b_lo, b_hi, out=v_all[:N])
+                ops.twohot_decode(z0, b_lo, b_hi, out=v_all[:N], space=v_space)
         elif self._slow_value:
             # the returns' values and bootstrap row come from the slow target on all Hm * N rows; the online head runs on
             # the rows its own loss reads
@@ -959,7 +1009,7 @@ class Dreamer:
                      and os.environ.get("REPO_VALUE_ONE_CHAIN", "1") == "1")
         if dyn:
             if twohot:   # dv (return_norm's scalar already in it) -> (Hm * N, K) through the head the returns were built from
-                dzt = ops.twohot_decode_bwd(zt, b_lo, b_hi, dv.view(-1))
+                dzt = ops.twohot_decode_bwd(zt, b_lo, b_hi, dv.view(-1), space=v_space)
                 ops.mlp_bwd(ps if self._slow_value else pv, feats, vt_hid, dzt, dparams=None, dx=dfeat, act=act_v)
             elif self._slow_value:
                 ops.mlp_bwd(ps, feats, vt_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
@@ -969,7 +1019,8 @@ class Dreamer:
             else:
                 ops.mlp_bwd(pv, feats, v_hid, dv.view(Hm * N, 1), dparams=None, dx=dfeat, act=act_v)
             if self._rew_twohot:   # dr (return_norm's scalar already in it) -> (nr_, K) through the decode's reverse
-                dzr = ops.twohot_decode_bwd(zr, self._reward_low, self._reward_high, dr.view(-1)[:nr_])
+                dzr = ops.twohot_decode_bwd(zr, self._reward_low, self._reward_high, dr.view(-1)[:nr_],
+                                            space=self._reward_space)
                 ops.mlp_bwd(pw, feats[:nr_], r_hid, dzr, dparams=None, dx=dfeat[:nr_], accumulate_dx=True, act=act_w)
             else:
                 ops.mlp_bwd(pw, feats[:nr_], r_hid, dr.view(Hm * N, 1)[:nr_], dparams=None, dx=dfeat[:nr_],
@@ -982,7 +1033,23 @@ class Dreamer:
         side.wait_stream(main)  # after the value head's backward above read the weights
         with torch.cuda.stream(side):
             if twohot:   # v_sums = [sum w CE, sum w]: the two slots of the scalar head's sums
-                v_sums, dz2 = ops.twohot_nll(z_on, returns.view(-1), weights, b_lo, b_hi, 1.0 / ((Hm - 1) * gN))
+                v_slow = None
+                if self._value_reg > 0.0:
+                    # config.value_slow_reg: the slow copy's DECODED value on the critic's nv rows, held
+                    # constant, is a second target of the same launch.  Where the returns read the copy it is decoded
+                    # already; otherwise one forward of the copy on those rows and one decode.
+                    if self._slow_value:
+                        v_slow = vt_pred.view(-1)[:nv]
+                    else:
+                        ps, _ = self._pg(self.slow_value_model)
+                        z_sl = ops.twohot_rows(nv, K, dev)
+                        ops.mlp_fwd(ps, feats[:nv], out=z_sl, act=act_v)
+                        v_slow = ops.twohot_decode(z_sl, b_lo, b_hi, space=v_space).view(-1)
+                v_sums, dz2 = ops.twohot_nll(z_on, returns.view(-1), weights, b_lo, b_hi, 1.0 / ((Hm - 1) * gN),
+                                             space=v_space, target_b=v_slow, reg=self._value_reg)
+                if v_slow is not None:   # [sum w CE_b]: one more slot of the update's one copy
+                    self._pending_vreg = v_sums[2:3]
+                v_sums = v_sums[:2]
                 ops.mlp_bwd(pv, feats[:nv], [h[:nv] for h in v_hid], dz2, dparams=gv, dx=None, act=act_v)
             elif not one_chain:   # (slow target: v_pred and v_hid have the nv rows already)
                 v_sums, dv2 = ops.scalar_nll(v_pred.view(-1)[:nv], returns.view(-1), weights, 1.0 / ((Hm - 1) * gN))
@@ -1048,6 +1115,10 @@ class Dreamer:
             rfs, self._pending_rf = self._pending_rf, None
             rfs.record_stream(cur)
             xs = torch.cat([xs, rfs])
+        if self._value_reg > 0.0:   # config.value_slow_reg: [sum w CE_b], behind actor_grad's
+            vrs, self._pending_vreg = self._pending_vreg, None
+            vrs.record_stream(cur)
+            xs = torch.cat([xs, vrs])
         if self._return_norm:   # config.return_norm: [scale, 1 / scale, lo, hi] -- no sums, the same on every rank: they
             rns, self._pending_rn = self._pending_rn, None   # ride behind the extra gradient norms, which are not summed
             rns.record_stream(cur)
@@ -1129,6 +1200,9 @@ class Dreamer:
                                        + (self._kl_dyn + self._kl_rep) * out["train/kl_loss"])
         else:
             out["train/model_loss"] = out["train/obs_loss"] + out["train/reward_loss"] + out["train/kl_loss"]
+        vreg = None
+        if self._value_reg > 0.0:   # [.., sum w CE_b] (see _log_update)
+            xsums, vreg = xsums[:-1], xsums[-1]
         rf = None
         if self._actor_mix < 1.0:   # [.., sum w adv logp, sum logp] (see _log_update)
             xsums, rf = xsums[:-2], xsums[-2:]
@@ -1150,6 +1224,9 @@ class Dreamer:
                                    - c.latent_ent_coef * latent_entropy)
         if self._twohot:   # vsq = sum w CE: a cross-entropy, no Normal constant
             out["train/value_loss"] = vsq / ((Hm - 1) * gN)
+            if vreg is not None:   # the total, and the regulariser's own weighted mean
+                out["train/value_loss"] = (vsq + self._value_reg * vreg) / ((Hm - 1) * gN)
+                out["train/value_reg"] = vreg / _vn if _vn > 0 else float("nan")
         elif self._pcont:   # ret = sum w R, _vn = sum w: the weighted means over the (Hm - 1) * gN elements
             out["train/value_loss"] = (vsq + 0.5 * LOG_2PI * _vn) / ((Hm - 1) * gN)
         else:
@@ -1404,7 +1481,7 @@ class Dreamer:
         }
         if self._pcont:
             params["pcont_model"] = sd(self.pcont_model)
-        if self._slow_value:   # the value head's key names; its phase is value_optimizer's step count
+        if self._slow_copy:   # the value head's key names; its phase is value_optimizer's step count
             params["slow_value_model"] = sd(self.slow_value_model)
         if self._return_norm:   # the running low / high order statistics of the imagined returns
             params["return_norm"] = self._return_state.detach().clone()
@@ -1460,7 +1537,7 @@ class Dreamer:
     def load_param_dict(self, params):
         self._check_value_head("value_model", self.value_model, params["value_model"])
         self._check_reward_head(params["reward_model"])
-        if self._slow_value and "slow_value_model" in params:
+        if self._slow_copy and "slow_value_model" in params:
             self._check_value_head("slow_value_model", self.slow_value_model, params["slow_value_model"])
         # config.optimizer: every optimiser entry's rule is checked before anything -- a weight, the step
         # count -- is taken from the checkpoint
@@ -1474,7 +1551,7 @@ class Dreamer:
         self.value_optimizer.load_state_dict(params["value_optimizer"])
         if self._pcont and "pcont_model" in params:   # optional, like the reference's optional modules
             self._load_module(self.pcont_model, params["pcont_model"])
-        if self._slow_value:
+        if self._slow_copy:
             if "slow_value_model" in params:
                 self._load_module(self.slow_value_model, params["slow_value_model"])
             else:   # a checkpoint written with the key off: the hard update at step 0, from the head just loaded

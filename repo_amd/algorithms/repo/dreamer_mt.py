@@ -44,6 +44,8 @@ class MultitaskDreamer(Dreamer):
     _BUILDS_REWARD_DIST = False   # reward_dist="twohot": built and tested for Dreamer and RePo
     _BUILDS_OBS_SYMLOG = False   # obs_symlog=True: built and tested for Dreamer and RePo on state vectors
     _BUILDS_KL_SCALES = False   # kl_dyn_scale / kl_rep_scale: built and tested for Dreamer
+    _BUILDS_VALUE_SLOW_REG = False   # value_slow_reg > 0: built and tested for Dreamer and RePo
+    _BUILDS_BIN_SPACE = False   # value_bin_space / reward_bin_space="symexp": built and tested for Dreamer and RePo
 
     def __init__(self, config, env, eval_env, logger):
         super().__init__(config, env, eval_env, logger)

@@ -52,6 +52,8 @@ class FinetunedRePo(RePo):
     _BUILDS_REWARD_DIST = False   # reward_dist="twohot": built and tested for Dreamer and RePo
     _BUILDS_OBS_SYMLOG = False   # obs_symlog=True: built and tested for Dreamer and RePo on state vectors
     _BUILDS_KL_SCALES = False   # kl_dyn_scale / kl_rep_scale: built and tested for Dreamer
+    _BUILDS_VALUE_SLOW_REG = False   # value_slow_reg > 0: built and tested for Dreamer and RePo
+    _BUILDS_BIN_SPACE = False   # value_bin_space / reward_bin_space="symexp": built and tested for Dreamer and RePo
     _BUILDS_SYMBOLIC = False   # pixel_obs=False: train_encoder runs the conv encoder's passes (the reference pins uint8 frames)
     _BUILDS_CONV_PRECISION = False   # conv_precision="high": built and tested for Dreamer and RePo
 
@@ -173,6 +175,8 @@ class CalibratedRePo(RePo):
     _BUILDS_REWARD_DIST = False   # reward_dist="twohot": built and tested for Dreamer and RePo
     _BUILDS_OBS_SYMLOG = False   # obs_symlog=True: built and tested for Dreamer and RePo on state vectors
     _BUILDS_KL_SCALES = False   # kl_dyn_scale / kl_rep_scale: built and tested for Dreamer
+    _BUILDS_VALUE_SLOW_REG = False   # value_slow_reg > 0: built and tested for Dreamer and RePo
+    _BUILDS_BIN_SPACE = False   # value_bin_space / reward_bin_space="symexp": built and tested for Dreamer and RePo
     _BUILDS_SYMBOLIC = False   # pixel_obs=False: the calibration frames are paired pixel frames (uint8, 6 channels)
     _BUILDS_CONV_PRECISION = False   # conv_precision="high": built and tested for Dreamer and RePo
     _LOG_KEYS = ("f_loss_src", "f_loss_tgt", "f_kl", "aln_loss", "calib_loss", "encoder_loss")

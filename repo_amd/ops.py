@@ -1222,16 +1222,27 @@ def twohot_rows(rows, K, device):
     return torch.empty(rows, ld, dtype=torch.float32, device=device)[:, :K]
 
 
-def twohot_decode(logits, low, high, out=None, want_mean=False):
+TWOHOT_SPACES = {"symlog": 0, "symexp": 1}   # config.value_bin_space / reward_bin_space: the kernels' `space`
+
+
+def twohot_decode(logits, low, high, out=None, want_mean=False, space="symlog"):
     """logits (rows, K) with contiguous rows at any pitch -> v (rows, 1) = symexp(sum_k softmax(logits)_k b_k), written into
     `out` (rows elements, contiguous) where given; want_mean: -> (v, m) with m (rows,) the mean in symlog space
-    (include/repo_hip.h, repo_twohot_decode)."""
+    (include/repo_hip.h, repo_twohot_decode).  space="symexp" (DESIGN.md 6r): v = sum_k p_k symexp(b_k), and m is v
+    (repo_twohot_decode_x)."""
     rows, K = logits.shape
     dev = logits.device
     if out is None:
         out = torch.empty(rows, 1, dtype=torch.float32, device=dev)
     assert out.numel() == rows
     m = torch.empty(rows, dtype=torch.float32, device=dev) if want_mean else None
+    if TWOHOT_SPACES[space]:
+        check(
+            lib().repo_twohot_decode_x(rows, K, _ptr(logits), _ld(logits), float(low), float(high), TWOHOT_SPACES[space],
+                                       _ptr(_f32c(out)), _ptr(m), _stream()),
+            "repo_twohot_decode_x",
+        )
+        return (out, m) if want_mean else out
     check(
         lib().repo_twohot_decode(rows, K, _ptr(logits), _ld(logits), float(low), float(high), _ptr(_f32c(out)), _ptr(m),
                                  _stream()),
@@ -1240,14 +1251,23 @@ def twohot_decode(logits, low, high, out=None, want_mean=False):
     return (out, m) if want_mean else out
 
 
-def twohot_decode_bwd(logits, low, high, g, out=None, gmul=None):
+def twohot_decode_bwd(logits, low, high, g, out=None, gmul=None, space="symlog"):
     """dlogits (rows, K) = g (|v| + 1) p (b - m), the derivative of twohot_decode's v times g (rows elements); gmul: a
-    one-element device tensor multiplied in, or None (include/repo_hip.h, repo_twohot_decode_bwd)."""
+    one-element device tensor multiplied in, or None (include/repo_hip.h, repo_twohot_decode_bwd).  space="symexp":
+    g p (B - v) (repo_twohot_decode_bwd_x)."""
     rows, K = logits.shape
     assert g.numel() == rows and (gmul is None or gmul.numel() == 1)
     if out is None:
         out = twohot_rows(rows, K, logits.device)
     assert out.shape == logits.shape
+    if TWOHOT_SPACES[space]:
+        check(
+            lib().repo_twohot_decode_bwd_x(rows, K, _ptr(logits), _ld(logits), float(low), float(high),
+                                           TWOHOT_SPACES[space], _ptr(_f32c(g)), _ptr(out), _ld(out),
+                                           _ptr(_f32c(gmul)) if gmul is not None else None, _stream()),
+            "repo_twohot_decode_bwd_x",
+        )
+        return out
     check(
         lib().repo_twohot_decode_bwd(rows, K, _ptr(logits), _ld(logits), float(low), float(high), _ptr(_f32c(g)), _ptr(out),
                                      _ld(out), _ptr(_f32c(gmul)) if gmul is not None else None, _stream()),
@@ -1256,21 +1276,36 @@ def twohot_decode_bwd(logits, low, high, g, out=None, gmul=None):
     return out
 
 
-def twohot_nll(logits, returns, weights, low, high, scale, want_grad=True, out=None, dlogits=None):
+def twohot_nll(logits, returns, weights, low, high, scale, want_grad=True, out=None, dlogits=None, space="symlog",
+               target_b=None, reg=0.0):
     """The two-hot cross-entropy of logits (rows, K) against returns (rows elements), weights (rows elements) or None for
     ones (include/repo_hip.h, repo_twohot_nll) -> (sums2 = [sum w CE, sum w], dlogits (rows, K) = scale w (p - t) or
-    None)."""
+    None).  With space="symexp" or a target_b (rows elements, weighed by reg) the launch is repo_twohot_nll_x's and the
+    sums are three: [sum w CE_a, sum w, sum w CE_b], dlogits = scale w ((1 + reg) p - t_a - reg t_b)."""
     rows, K = logits.shape
     dev = logits.device
     assert returns.numel() == rows and (weights is None or weights.numel() == rows)
+    assert target_b is None or target_b.numel() == rows
     if want_grad and dlogits is None:
         dlogits = twohot_rows(rows, K, dev)
     if not want_grad:
         dlogits = None
     assert dlogits is None or dlogits.shape == logits.shape
+    extended = bool(TWOHOT_SPACES[space]) or target_b is not None
     if out is None:
-        out = torch.empty(2, dtype=torch.float32, device=dev)
+        out = torch.empty(3 if extended else 2, dtype=torch.float32, device=dev)
     ws = reduce_ws(dev)
+    if extended:
+        assert out.numel() == 3
+        check(
+            lib().repo_twohot_nll_x(rows, K, _ptr(logits), _ld(logits), _ptr(_f32c(returns)),
+                                    _ptr(_f32c(target_b)) if target_b is not None else None, float(reg),
+                                    _ptr(_f32c(weights)) if weights is not None else None, float(low), float(high),
+                                    TWOHOT_SPACES[space], float(scale), _ptr(dlogits),
+                                    _ld(dlogits) if dlogits is not None else 0, _ptr(out), _ptr(ws), ws.numel(), _stream()),
+            "repo_twohot_nll_x",
+        )
+        return out, dlogits
     check(
         lib().repo_twohot_nll(rows, K, _ptr(logits), _ld(logits), _ptr(_f32c(returns)),
                               _ptr(_f32c(weights)) if weights is not None else None, float(low), float(high), float(scale),
